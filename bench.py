@@ -1,7 +1,13 @@
 """Benchmark: rendered Mpix/s, fwd+bwd, 1M Gaussians at 1920x1080 (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver, N > 1)
+
+A plain run sets up, spins up and warms up, times the K steps, writes the
+last timed step's outputs if --dump-outputs is given, and prints the result
+line (metric, value, unit, ms_per_step, the workload and the graph replay's
+state).  Everything under "With --full" below takes runs of its own after
+the timed region and is off by default.
 
 One step on each rank = one training step of one view: zero_grad ->
 GaussianRenderer.render -> backward of a fixed random cotangent on
@@ -16,7 +22,16 @@ resident in HBM before the timed region.  Before the W warm-up steps,
 to its steady clock.  `value` = all ranks' pixels /
 max-over-ranks step time.
 
-Also reported: the roofline of the dominant kernel (HIP events on the
+--dump-outputs DIR writes what a caller of the last timed step receives as
+DIR/<name>.npy (float32): image, alpha, depth and the visibility filter of
+the rendered frame, the parameters Adam wrote (param_<name>), and the
+gradients where the step materialises them (grad_<name>: not with the
+optimizer fused into the backward).  At most 64 MB in all: when the arrays
+exceed that, each large one is a fixed, seeded sample of its elements (the
+same elements in every run).  The scene, the camera and the cotangents are
+seeded, so two runs with the same arguments have identical inputs.
+
+With --full, also reported: the roofline of the dominant kernel (HIP events on the
 kernels' own stream, averaged over the timed steps), priced by SURVEY.md
 8(d)'s algorithmic byte and flop models from the frame's work counters
 (R, E, C, M), against the 8 TB/s spec and a copy kernel measured on the box;
@@ -72,8 +87,16 @@ def parse():
     ap.add_argument("--gaussians", type=int, default=None, help="override the preset's Gaussian count")
     ap.add_argument("--width", type=int, default=None, help="override the preset's image width")
     ap.add_argument("--height", type=int, default=None, help="override the preset's image height")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all; large arrays as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the per-stage "
+                         "breakdown, the frame's work counters and roofline, the CPU baseline and PSNR, and "
+                         "(N > 1 or --force-dist) the collective's share of the step")
     ap.add_argument("--no-optimizer", action="store_true", help="time render fwd+bwd only")
-    ap.add_argument("--diag-steps", type=int, default=5, help="untimed steps for the per-stage breakdown")
+    ap.add_argument("--diag-steps", type=int, default=5,
+                    help="(--full) untimed steps for the per-stage breakdown")
     # MI355X clocks ramp over the first ~60 ms of load: with 5 warm-up steps the
     # timed steps ran 1.25 ms, with 50 or 200 1.19 (same box, profiles/r02/warmup.log).
     # A fixed count (not a time) so that every rank runs the same collectives.
@@ -82,7 +105,7 @@ def parse():
     ap.add_argument("--spinup-steps", type=int, default=None,
                     help="untimed steps before the --warmup steps, for the GPU (and host CPU) clock ramp; "
                          "default ~60 ms or more of steps: 50 at C3, more for the smaller presets")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) leave out the CPU baseline and PSNR")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="an extra oracle thread count for the CPU sweep (16..256 and the CPU limit always run)")
     ap.add_argument("--dist-backend", default="nccl",
@@ -170,6 +193,58 @@ def copy_peak_gbs(dev, nbytes=1 << 30, reps=10):
     del src, dst
     torch.cuda.empty_cache()
     return gbs
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all arrays together (the limit is 64 MB, .npy headers included)
+
+
+def dump_arrays(path, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write each tensor of `arrays` (name -> tensor) as path/<name>.npy in
+    float32.  If they fit the budget together, whole and in their own shape;
+    otherwise every array over an equal share of the budget is written as a
+    1-D sample of that many of its (flattened) elements, at indices drawn
+    once per array from a generator seeded with 0, in increasing order: the
+    same elements for the same shapes, whatever the values."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    whole = 4 * sum(t.numel() for t in arrays.values()) <= budget_bytes
+    share = budget_bytes // 4 // max(1, len(arrays))
+    rng = np.random.default_rng(0)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if not whole and t.numel() > share:
+            idx = np.sort(rng.choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arr = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
+def step_outputs(gstep, frame, model, params, opt):
+    """What a caller of the last timed step receives: the frame (image,
+    alpha, depth, visibility filter), the parameters Adam wrote (its shadow
+    outputs) and the gradients where the step leaves them in memory -- from
+    the replayed graph's buffers, or from the eager step's render() result
+    and .grad tensors."""
+    names = {id(model._xyz): "xyz", id(model._features_dc): "features_dc", id(model._opacity): "opacity",
+             id(model._scaling): "scaling", id(model._rotation): "rotation"}
+    replayed = gstep is not None and gstep.graph is not None and not gstep.disabled
+    if replayed:
+        arrays = {"image": gstep.image, "alpha": gstep.alpha, "depth": gstep.depth,
+                  "visibility_filter": gstep.vis}
+        grads = [] if gstep.fused_adam else list(gstep.leaf_grad)
+    else:
+        arrays = {k: frame[k] for k in ("image", "alpha", "depth", "visibility_filter")}
+        grads = [(p, p.grad) for p in params if p.grad is not None]
+    for p, g in grads:
+        arrays["grad_" + names[id(p)]] = g.reshape(p.shape)
+    if opt is not None:
+        for p in params:
+            if p in opt.param_out:
+                arrays["param_" + names[id(p)]] = opt.param_out[p]
+    return arrays
 
 
 def main():
@@ -298,7 +373,7 @@ def main():
     if gstep is not None:
         gstep.finish()  # (checks the last replay; a redo would show in graph_info below)
         gstep.timing = False
-        bwd_live = gstep.blend_backward_ms()
+        bwd_live = gstep.blend_backward_ms() if a.full else []
         graph_info = {"replayed": True, "nodes": gstep.graph.num_nodes if gstep.graph else None,
                       "steps_redone_in_timed_region": sum(k for _, k in gstep.redone) - redone0,
                       "redone": gstep.redone, "disabled": gstep.disabled,
@@ -318,21 +393,27 @@ def main():
         dt = float(t.item())
     StageTimer.only = None
     StageTimer.reset()
-    coll = collective_share(a, dist, dev, reducer, model, eager_step, frames, dt) if reducer is not None else None
-    # the per-stage breakdown from the stage-by-stage path (the same kernels;
-    # the frame entry points would time only the blend backward)
-    from mini3dgs_amd import rasterizer as _RZ
-    frame_calls, _RZ._FRAME_CALLS = _RZ._FRAME_CALLS, False
-    for _ in range(a.diag_steps):
-        eager_step()
-        frames = frames[-1:]
-    _RZ._FRAME_CALLS = frame_calls
-    stages = {k: sum(v) / len(v) for k, v in StageTimer.durations_ms().items()}
-    StageTimer.enabled = False
     ms_per_step = 1000.0 * dt / a.steps
     mpix = world * H * W * a.steps / dt / 1e6
+    dumped = None
+    if a.dump_outputs and rank == 0:  # (before any further step: the last timed step's outputs)
+        dumped = dump_arrays(a.dump_outputs, step_outputs(gstep, frames[-1] if frames else None, model, params, opt))
+    coll, stages = None, {}
+    if a.full:
+        coll = collective_share(a, dist, dev, reducer, model, eager_step, frames, dt) if reducer is not None else None
+        # the per-stage breakdown from the stage-by-stage path (the same kernels;
+        # the frame entry points would time only the blend backward)
+        from mini3dgs_amd import rasterizer as _RZ
+        frame_calls, _RZ._FRAME_CALLS = _RZ._FRAME_CALLS, False
+        for _ in range(a.diag_steps):
+            eager_step()
+            frames = frames[-1:]
+        _RZ._FRAME_CALLS = frame_calls
+        stages = {k: sum(v) / len(v) for k, v in StageTimer.durations_ms().items()}
+    StageTimer.enabled = False
 
-    if rank == 0:
+    counters, report = {}, {}
+    if rank == 0 and a.full:
         # --- roofline of the dominant kernel -------------------------------
         from mini3dgs_amd.rasterizer import forward_pipeline  # noqa: F401
         tiles_x, tiles_y = (W + 15) // 16, (H + 15) // 16
@@ -408,20 +489,9 @@ def main():
                     "pixels_over_1e-4": int((np.abs(err).max(axis=0) > 1e-4).sum()),
                     "ref": "oracle/gs_oracle.c on the same frame (CPU restatement of renderer.py, "
                            "pinned to the reference's own outputs); db None = bit-identical images"}
-        wl = workload_name(n, W, H)
-        line = {
-            "metric": METRIC, "value": round(mpix, 3), "unit": "Mpix/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "spinup_steps": a.spinup_steps, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{wl}: {n:,} synthetic Gaussians (SURVEY 8d), {W}x{H}, 16x16 tiles, "
-                                   "render fwd+bwd" + (" + grad all-reduce" if reducer is not None else "")
-                                   + ("" if opt is None else " + Adam step"),
-                       "preset": wl,
-                       "gaussians": n, "width": W, "height": H, "views_per_step": world,
-                       "parallelism": f"dp{world} (one view per GPU)", "visible": M, "tile_touches": T,
-                       "records_consumed": R, "evaluated_pairs": E, "contributing_pairs": Cc,
-                       "live_entry_cells": live_pairs},
-            "graph": graph_info,
+        counters = {"visible": M, "tile_touches": T, "records_consumed": R, "evaluated_pairs": E,
+                    "contributing_pairs": Cc, "live_entry_cells": live_pairs}
+        report = {
             "stages_ms": {k: round(v, 4) for k, v in stages.items()},
             "stages_note": f"HIP-event intervals from {a.diag_steps} diagnostic steps after the timed region, "
                            "run stage by stage (GS_FRAME_CALLS=0 path: the same kernels as the timed steps' frame "
@@ -432,18 +502,35 @@ def main():
             "cpu_baseline": cpu,
             "psnr_vs_ref": psnr,
         }
+    if rank == 0:
+        wl = workload_name(n, W, H)
+        line = {
+            "metric": METRIC, "value": round(mpix, 3), "unit": "Mpix/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "spinup_steps": a.spinup_steps, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": a.full,
+            "config": {"workload": f"{wl}: {n:,} synthetic Gaussians (SURVEY 8d), {W}x{H}, 16x16 tiles, "
+                                   "render fwd+bwd" + (" + grad all-reduce" if reducer is not None else "")
+                                   + ("" if opt is None else " + Adam step"),
+                       "preset": wl,
+                       "gaussians": n, "width": W, "height": H, "views_per_step": world,
+                       "parallelism": f"dp{world} (one view per GPU)", **counters},
+            "graph": graph_info,
+            **report,
+        }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if reducer is not None:
-            # steps that issued collectives: spin-up, warm-up, the timed steps,
-            # collective_share's timing run (its no-collective run issues none)
-            # and the diagnostic steps
-            nsteps = a.spinup_steps + a.warmup + 2 * a.steps + a.diag_steps
+            # steps that issued collectives: spin-up, warm-up, the timed steps, and
+            # with --full collective_share's timing run (its no-collective run
+            # issues none) and the diagnostic steps
+            nsteps = a.spinup_steps + a.warmup + a.steps + ((a.steps + a.diag_steps) if a.full else 0)
             line["allreduce"] = {"ranges_per_step": reducer.overlap_chunks(), "pipelined_adam": opt is not None,
                                  "host_us_per_step": {k: round(1e6 * v / nsteps, 1) for k, v in reducer.host_s.items()},
                                  "avg": reducer._avg, "native": reducer.native_status["native"],
                                  "rccl_nranks": reducer.native_status["rccl_nranks"],
                                  "self_check_err": reducer.native_status["self_check_err"],
                                  "fallback_reason": reducer.native_status["fallback_reason"]}
-            line["allreduce"].update(coll)
+            line["allreduce"].update(coll or {})
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -14,8 +14,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--config", "C1", "--steps", "8", "--warmup", "2", "--spinup-steps", "3", "--diag-steps", "2",
-        "--no-cpu-baseline"]
+ARGS = ["--full", "--config", "C1", "--steps", "8", "--warmup", "2", "--spinup-steps", "3", "--diag-steps", "2",
+        "--no-cpu-baseline"]  # (--full: the collective's share takes runs of its own)
 
 
 def _free_port():

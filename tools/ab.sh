@@ -9,7 +9,7 @@ mkdir -p "$R/gpurun_out/ab"
 for ((i = 0; i < rounds; i++)); do
   for lib in "$@"; do
     n=$(basename "$lib" .so)
-    GS_LIB_PATH=$R/$lib timeout -k 10 200 python "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline \
+    GS_LIB_PATH=$R/$lib timeout -k 10 200 python "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline \
       > "$R/gpurun_out/ab/${n}_$i.log" 2>&1 || { echo "bench failed: $lib"; exit 1; }
     python3 - "$R/gpurun_out/ab/${n}_$i.log" "$n" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for ((i = 0; i < rounds; i++)); do
     n=${ent%%:*}
     kv=${ent#*:}
     if [ "$kv" = "-" ]; then envs=(); else envs=("$kv"); fi
-    env "${envs[@]}" timeout -k 10 200 python "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline \
+    env "${envs[@]}" timeout -k 10 200 python "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline \
       > "$R/gpurun_out/ab/${n}_$i.log" 2>&1 || { echo "bench failed: $ent"; exit 1; }
     python3 - "$R/gpurun_out/ab/${n}_$i.log" "$n" <<'PY'
 import json, sys

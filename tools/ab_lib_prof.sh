@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   n=$(basename "$lib" .so)
   GS_LIB_PATH=$R/$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o run --output-format csv \
-    -- python3 "$R/bench.py" --steps 30 --warmup 5 --diag-steps 0 --no-cpu-baseline > "$O/prof_$n.log" 2>&1 \
+    -- python3 "$R/bench.py" --full --steps 30 --warmup 5 --diag-steps 0 --no-cpu-baseline > "$O/prof_$n.log" 2>&1 \
     || { echo "rocprof failed: $lib"; tail -5 "$O/prof_$n.log"; exit 1; }
   python3 "$R/tools/timed_kernel_stats.py" "$O/prof_$n/run_kernel_trace.csv" 30 > "$O/kernel_stats_$n.txt" || true
   echo "== $n $(python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith('{')][-1]); print(d['ms_per_step'])" "$O/prof_$n.log") ms/step"

@@ -14,7 +14,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in "$@"; do
   n=$(basename "$lib" .so)
   GS_LIB_PATH=$R/$lib timeout -s KILL 120 rocprofv3 --pmc $ctr --kernel-include-regex 'k_blend' -d "$O/$n" -o pmc \
-    --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --spinup-steps 2 --no-cpu-baseline > "$O/$n.log" 2>&1 \
+    --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --spinup-steps 2 --no-cpu-baseline > "$O/$n.log" 2>&1 \
     || { echo "pmc failed: $n"; exit 1; }
   python3 - "$O/$n/pmc_counter_collection.csv" "$n" <<'PY'
 import csv, collections, re, sys

@@ -13,7 +13,7 @@ mkdir -p "$O"
 for ((i = 0; i < rounds; i++)); do
   for t in "$@"; do
     n=$(echo "$t" | tr '/.' '__')
-    (cd "$R/$t" && timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline) > "$O/${n}_$i.log" 2>&1 \
+    (cd "$R/$t" && timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline) > "$O/${n}_$i.log" 2>&1 \
       || { echo "bench failed: $t"; tail -5 "$O/${n}_$i.log"; exit 1; }
     python3 - "$O/${n}_$i.log" "$t" <<'PY'
 import json, sys
@@ -28,7 +28,7 @@ cd /tmp && export TMPDIR=/tmp
 for t in "$@"; do
   n=$(echo "$t" | tr '/.' '__')
   (cd "$R/$t" && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$n" -o run --output-format csv \
-    -- python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline > "$O/prof_$n.log" 2>&1) || { echo "rocprof failed: $t"; exit 1; }
+    -- python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > "$O/prof_$n.log" 2>&1) || { echo "rocprof failed: $t"; exit 1; }
   python3 "$R/tools/timed_kernel_stats.py" "$O/prof_$n/run_kernel_trace.csv" 35 > "$O/kernel_stats_$n.txt" || true
   echo "== $t"; head -8 "$O/kernel_stats_$n.txt"
 done

@@ -12,7 +12,7 @@ while read -r grp; do
   [ -z "$grp" ] && continue
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-include-regex 'k_' -d "$OUT/p$i" -o pmc --output-format csv \
-    -- python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }
+    -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }
 done <<'GROUPS'
 FETCH_SIZE
 WRITE_SIZE

@@ -8,7 +8,7 @@ O=$R/gpurun_out/b4
 mkdir -p "$O"
 cd "$R"
 GS_ALLREDUCE_CHUNKS=4 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-  --master-port 29581 bench.py --gpus 1 --steps 20 --warmup 3 --force-dist --no-cpu-baseline \
+  --master-port 29581 bench.py --full --gpus 1 --steps 20 --warmup 3 --force-dist --no-cpu-baseline \
   > "$O/rccl_world1.log" 2>&1 || { echo "rccl world1 failed"; tail -20 "$O/rccl_world1.log"; exit 1; }
 python3 -c "import json;l=json.loads(open('$O/rccl_world1.log').read().strip().splitlines()[-1]);print('world1 rccl', l['ms_per_step'], l['allreduce'])" && \
 bash tools/r04_dist.sh && \

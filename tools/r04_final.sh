@@ -5,6 +5,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
+LOG=$(mktemp)  # the bench line after the PMC passes
 bash tools/round_check.sh r04final && bash tools/pmc_run.sh pmc_r04final && \
-  timeout -k 10 300 python bench.py --no-cpu-baseline > gpurun_out/r04final/bench_after_pmc.log 2>&1 && \
-  python3 -c "import json;l=json.loads([x for x in open('gpurun_out/r04final/bench_after_pmc.log').read().splitlines() if x.startswith('{')][-1]);r=l['roofline'];print('bench', l['value'], l['ms_per_step'], 'traffic', r['traffic'], r['traffic_source'].get('build_match'))"
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$LOG" 2>&1 && \
+  python3 -c "import json,sys;l=json.loads([x for x in open(sys.argv[1]).read().splitlines() if x.startswith('{')][-1]);r=l['roofline'];print('bench', l['value'], l['ms_per_step'], 'traffic', r['traffic'], r['traffic_source'].get('build_match'))" "$LOG"

@@ -10,10 +10,10 @@ CFG=${1:-C3}
 mkdir -p "$O"
 cd "$R"
 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29581 timeout -k 10 300 \
-  python bench.py --force-dist --config "$CFG" --no-cpu-baseline > "$O/world1_native_$CFG.log" 2>&1 \
+  python bench.py --full --force-dist --config "$CFG" --no-cpu-baseline > "$O/world1_native_$CFG.log" 2>&1 \
   || { echo "world1 native failed"; tail -30 "$O/world1_native_$CFG.log"; exit 1; }
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29582 bench.py --gpus 2 --config "$CFG" --dist-backend gloo --no-cpu-baseline \
+  --master-port 29582 bench.py --full --gpus 2 --config "$CFG" --dist-backend gloo --no-cpu-baseline \
   > "$O/gloo2_$CFG.log" 2>&1 || { echo "gloo2 failed"; tail -30 "$O/gloo2_$CFG.log"; exit 1; }
 for f in "$O/world1_native_$CFG.log" "$O/gloo2_$CFG.log"; do
   python3 -c "

@@ -4,7 +4,7 @@ per-unit models x the frame's counts), the PMC traffic of the same build
 of MI355X_MICROARCH.md; raw FETCH + WRITE beside it) and the timed-region
 kernel durations (tools/timed_kernel_stats.py output).
 
-The frame's counts come from a bench line (bench.py's `config`: gaussians,
+The frame's counts come from a `bench.py --full` line (its `config`: gaussians,
 visible M, tile touches T, records consumed R, live (entry, cell) pairs L,
 width x height) -- not from constants (a hard-coded L of
 11.54 M, two atomic requests per live pair, had overstated the gather's bytes).

@@ -13,7 +13,7 @@ mkdir -p "$O"
 rounds=${1:-3}
 run() {  # name, env...
   local n=$1; shift
-  env "$@" timeout -k 10 200 python "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$O/$n.log" 2>&1 || { echo "bench failed: $n"; tail -5 "$O/$n.log"; exit 1; }
+  env "$@" timeout -k 10 200 python "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$O/$n.log" 2>&1 || { echo "bench failed: $n"; tail -5 "$O/$n.log"; exit 1; }
   python3 - "$O/$n.log" "$n" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -29,11 +29,11 @@ cd /tmp && export TMPDIR=/tmp
 for v in base atomic; do
   ex="GS_LIB_PATH=$R/ab/$v.so"; [ $v = atomic ] && ex="$ex GS_BWD_ATOMIC=1"
   export GS_LIB_PATH=$R/ab/$v.so GS_BWD_ATOMIC=$([ $v = atomic ] && echo 1 || echo 0)
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$O/prof_$v" -o run --output-format csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline > "$O/prof_$v.log" 2>&1 || { echo "prof failed $v"; exit 1; }
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$O/prof_$v" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline > "$O/prof_$v.log" 2>&1 || { echo "prof failed $v"; exit 1; }
   j=0
   for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_ATOMIC_sum"; do
     j=$((j+1))
-    timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-include-regex 'k_blend_bwd|k_gather' -d "$O/pmc_${v}_$j" -o pmc --output-format csv -- python3 "$R/bench.py" --steps 3 --warmup 1 --spinup-steps 2 --no-cpu-baseline > "$O/pmc_${v}_$j.log" 2>&1 || { echo "pmc $v $grp failed"; exit 1; }
+    timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-include-regex 'k_blend_bwd|k_gather' -d "$O/pmc_${v}_$j" -o pmc --output-format csv -- python3 "$R/bench.py" --full --steps 3 --warmup 1 --spinup-steps 2 --no-cpu-baseline > "$O/pmc_${v}_$j.log" 2>&1 || { echo "pmc $v $grp failed"; exit 1; }
   done
 done
 unset GS_LIB_PATH GS_BWD_ATOMIC
