@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 21
+#define GS_ABI_VERSION 22
 #define GS_DEFAULT_TILE 16    /* renderer.py:24 tile_size default */
 #define GS_MAX_TILE 16384     /* tile_size in [1, GS_MAX_TILE]; the reference accepts any int, and a tile
                                  of at least max(W, H) renders the same as any larger one (one tile
@@ -412,6 +412,26 @@ gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream);
  * blend backward run in cell batches: batch b's sums are added after batch
  * b - 1's, a fixed order.  Reads vis, rects, pair_offset, g.n. */
 gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, gs_stream_t stream);
+
+/* ---- Backward of the projection, with the camera pose's gradient --------
+ * gs_project_backward (every d_* of bwd is written as there, bit for bit)
+ * plus dL/d(view) for cam.view = rows [R | t] of the world-to-camera matrix,
+ * which the reference's autograd reaches through Xc = Rv Xw + Tv and
+ * cov_cam = Rv Sigma Rv^T (renderer.py:150-168):
+ *   d_t = sum_g dXc,  d_R = sum_g dXc Xw^T + dC (R Sigma^T) + dC^T (R Sigma)
+ * and, with sh_degree > 0, through the view direction's origin
+ * cam.campos = -R^T t:  d_R[i][j] -= t[i] d_campos[j],
+ * d_t[i] -= sum_j R[i][j] d_campos[j].  R need not be orthonormal.
+ * The sum over Gaussians is deterministic (no atomics): each workgroup of 256
+ * Gaussians reduces in a fixed order into one row of pose_partials, and one
+ * workgroup sums the rows in index order and a fixed tree, in double. */
+typedef struct gs_project_pose_args {
+  gs_project_bwd_args bwd;     /* as gs_project_backward; order must be NULL */
+  double *pose_partials;       /* [pose_partial_rows, 16] workspace (contents undefined after the call) */
+  int64_t pose_partial_rows;   /* >= ceil(bwd.g.n / 256) */
+  float *d_view;               /* [12] out: rows [d_R | d_t], row-major 3x4 (zeros when bwd.g.n <= 0) */
+} gs_project_pose_args;
+gs_status gs_project_backward_pose(const gs_project_pose_args *a, gs_stream_t stream);
 
 /* ---- Adam step over several parameter tensors, one launch -----------------
  * SURVEY 8(f) row 1 (fused Adam), the optimizer the reference builds in

@@ -27,7 +27,7 @@ GS_RECORD_FLOATS = 12
 GS_PAIR_GRAD_FLOATS = 10
 GS_PARTIAL_STRIDE = 10  # floats between partials in pair_grads (dense; gs_partial_groups per entry)
 GS_NUM_COUNTERS = 8  # M, T, depth-bits min / max, frame status, T_eff (GS_NUM_COUNTERS in the header)
-GS_ABI_VERSION = 21
+GS_ABI_VERSION = 22
 # frame status bits (counters[4]; the pinned counters' [5]): what a device-resident
 # frame could not do on the device, so its step is redone on the host path
 GS_FRAME_NEED_CAPACITY, GS_FRAME_WINDOW_MISS, GS_FRAME_EMPTY = 1, 2, 4
@@ -109,6 +109,14 @@ class GsProjectBwdArgs(C.Structure):
         ("d_rotation", _vp), ("d_color_logits", _vp), ("d_opacity", _vp), ("d_sh_rest", _vp),
         ("slot_live", _vp), ("grad_sums", _vp), ("partial_groups", C.c_int32),
     ]
+
+
+GS_POSE_ROW = 16  # doubles per row of gs_project_pose_args.pose_partials; one row per 256 Gaussians
+GS_POSE_BLOCK = 256
+
+
+class GsProjectPoseArgs(C.Structure):
+    _fields_ = [("bwd", GsProjectBwdArgs), ("pose_partials", _vp), ("pose_partial_rows", C.c_int64), ("d_view", _vp)]
 
 
 class GsFrameBuffers(C.Structure):
@@ -196,6 +204,7 @@ EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
     "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_workspace_bytes", "gs_bin_count", "gs_bin_emit",
     "gs_tile_ranges", "gs_blend_live_words", "gs_tile_quads", "gs_partial_groups", "gs_blend_forward", "gs_blend_backward", "gs_project_backward",
+    "gs_project_backward_pose",
     "gs_blend_backward_groups", "gs_blend_backward_lane_stats", "gs_gather_partials", "gs_frame_workspace_bytes", "gs_tile_workspace_bytes", "gs_render_forward",
     "gs_render_backward", "gs_frame_offsets", "gs_tile_offsets", "gs_adam_step", "gs_project_backward_adam", "gs_loss_workspace_bytes", "gs_loss_forward", "gs_loss_backward",
     "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit",
@@ -238,6 +247,7 @@ def _declare(lib):
     lib.gs_blend_backward_lane_stats.argtypes = [P(GsBlendBwdArgs), _vp, _vp, _vp]
     lib.gs_project_backward.argtypes = [P(GsProjectBwdArgs), _vp]
     lib.gs_gather_partials.argtypes = [P(GsProjectBwdArgs), C.c_int32, _vp]
+    lib.gs_project_backward_pose.argtypes = [P(GsProjectPoseArgs), _vp]
     lib.gs_frame_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.gs_frame_workspace_bytes.restype = C.c_size_t
     lib.gs_tile_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
@@ -260,7 +270,7 @@ def _declare(lib):
     lib.gs_densify_emit.argtypes = [P(GsDensifyArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
-              "gs_project_backward", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit"):
+              "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -2168,8 +2168,19 @@ struct AdamOut {
   }
 };
 
-template <bool kHot, typename Sums, typename Out>
-__device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, int g, Sums sums, Out &out) {
+// kPose (gs_project_backward_pose, the generic configuration only): the
+// Gaussian's share of dL/d(view) is added to pose[kPoseVals] in double --
+// [0..8] d_R row-major, [9..11] d_t, [12..14] d_campos (the SH view
+// direction's origin) -- for the caller's workgroup reduction:
+//   d_t += dXc,  d_R += dXc Xw^T + dC (R S^T) + dC^T (R S),  d_campos -= dxyz_sh
+// with dXc the gradient at Xc = R Xw + t and dC the one at R S R^T; nothing
+// assumes an orthonormal R or a symmetric S.  Every early return below leaves
+// through this function only, so the caller's barrier is reached.
+constexpr int kPoseVals = 15;
+constexpr int kPoseRow = 16;  // doubles per row of the partial buffer
+template <bool kHot, bool kPose = false, typename Sums, typename Out>
+__device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, int g, Sums sums, Out &out,
+                                                double *pose = nullptr) {
   float scl_pre[3] = {0.f, 0.f, 0.f}, rot_pre[4] = {0.f, 0.f, 0.f, 0.f}, op_pre = 0.f;
   if constexpr (kHot) {
 #pragma unroll
@@ -2226,6 +2237,10 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
     const float dot = (dir[0] * dd[0] + dir[1] * dd[1]) + dir[2] * dd[2];
 #pragma unroll
     for (int j = 0; j < 3; ++j) dxyz_sh[j] = (dd[j] - dir[j] * dot) * inv_norm;
+    if constexpr (kPose) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) pose[12 + j] -= (double)dxyz_sh[j];
+    }
   }
   float dop = acc[5];
   if (a.g.opacity_is_logit) {  // through get_opacity's sigmoid, as torch's sigmoid_backward
@@ -2318,6 +2333,31 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
     for (int j = 0; j < 3; ++j)
       out(kOutXyz, g, j, (float)(R[j] * dX + R[4 + j] * dY + R[8 + j] * dZ + (double)dxyz_sh[j]), xv[j]);
   }
+  if constexpr (kPose) {
+    const double dXc[3] = {dX, dY, dZ}, Xw[3] = {xw, yw, zw};
+    double dVJd[6], dCd[9], RSt[9];  // dC = J^T dV J in double; R S^T beside RS = R S
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dVJd[k * 3 + j] = dVd[k * 2] * Jd[j] + dVd[k * 2 + 1] * Jd[3 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        dCd[i * 3 + j] = Jd[i] * dVJd[j] + Jd[3 + i] * dVJd[3 + j];
+        RSt[i * 3 + j] = (double)R[i * 4] * Sf[j * 3] + (double)R[i * 4 + 1] * Sf[j * 3 + 1] +
+                         (double)R[i * 4 + 2] * Sf[j * 3 + 2];
+      }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      pose[9 + i] += dXc[i];
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        pose[i * 3 + j] += dXc[i] * Xw[j] +
+                           (dCd[i * 3] * RSt[j] + dCd[i * 3 + 1] * RSt[3 + j] + dCd[i * 3 + 2] * RSt[6 + j]) +
+                           (dCd[i] * RS[j] + dCd[3 + i] * RS[3 + j] + dCd[6 + i] * RS[6 + j]);
+    }
+  }
   float J[6], dV[4];
 #pragma unroll
   for (int k = 0; k < 6; ++k) J[k] = (float)Jd[k];
@@ -2390,13 +2430,53 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
 // which serialised six round trips per thread in the generic instantiation).
 // kAdam (gs_project_backward_adam, kHot only): the parameters' Adam update
 // fused in, no gradient arrays written.
-template <bool kHot, bool kAdam = false>
-__global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a, FusedAdamArgs fa = {}) {
+// kPose (gs_project_backward_pose, neither kHot nor kAdam): the workgroup's
+// Gaussians' shares of dL/d(view) reduced in a fixed order -- down each wave
+// (shuffles at offsets 32..1), then the four waves in wave order through LDS
+// -- into row blockIdx.x of the [blocks, kPoseRow] double partials.  No
+// thread leaves before the barrier: one with k >= n adds zeros and touches
+// no memory.  The kernel's second argument is the instantiation's own.
+struct PoseArgs {
+  double *partials;
+};
+// sum of every thread's v[kPoseVals] (all kBlock threads call): the totals in
+// tot[0..kPoseVals) of LDS, visible to every thread on return
+__device__ __forceinline__ void pose_block_sum(double v[kPoseVals], double (&red)[kBlock / kWave][kPoseRow],
+                                               double (&tot)[kPoseRow]) {
+  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+#pragma unroll
+  for (int q = 0; q < kPoseVals; ++q) {
+    double x = v[q];
+#pragma unroll
+    for (int o = kWave / 2; o >= 1; o >>= 1) x += __shfl_down(x, o, kWave);
+    if (lane == 0) red[wave][q] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < kPoseRow) {
+    double x = 0.0;
+    if (threadIdx.x < kPoseVals) {
+      x = red[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < kBlock / kWave; ++w) x += red[w][threadIdx.x];
+    }
+    tot[threadIdx.x] = x;
+  }
+  __syncthreads();
+}
+
+template <bool kHot, bool kAdam = false, bool kPose = false>
+__global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a,
+                                                        std::conditional_t<kPose, PoseArgs, FusedAdamArgs> fa = {}) {
+  static_assert(!kPose || (!kHot && !kAdam), "the pose reduction is the generic instantiation's");
   const int k = blockIdx.x * kBlock + threadIdx.x;
-  if (k >= a.g.n) return;
-  if (kAdam && fa.skip_flag && *fa.skip_flag) return;  // (the replayed step's frame failed)
+  if constexpr (!kPose) {
+    if (k >= a.g.n) return;
+  }
+  if constexpr (kAdam) {
+    if (fa.skip_flag && *fa.skip_flag) return;  // (the replayed step's frame failed)
+  }
   // in depth order, consecutive threads own adjacent slot ranges
-  const int g = (!kHot && a.order) ? (int)a.order[k] : k;
+  const int g = (!kHot && !kPose && a.order) ? (int)a.order[k] : k;
   auto sums = [&](float acc[GS_PAIR_GRAD_FLOATS]) {
 #pragma unroll
     for (int k = 0; k < GS_PAIR_GRAD_FLOATS; ++k) acc[k] = 0.f;
@@ -2414,9 +2494,50 @@ __global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a, F
     AdamOut out;
     project_bwd_one<kHot>(a, g, sums, out);
     out.flush(fa, g);
+  } else if constexpr (kPose) {
+    __shared__ double red[kBlock / kWave][kPoseRow], tot[kPoseRow];
+    double pose[kPoseVals];
+#pragma unroll
+    for (int q = 0; q < kPoseVals; ++q) pose[q] = 0.0;
+    if (k < a.g.n) {
+      GradsOut out{a};
+      project_bwd_one<false, true>(a, g, sums, out, pose);
+    }
+    pose_block_sum(pose, red, tot);
+    if (threadIdx.x < kPoseRow) fa.partials[(size_t)blockIdx.x * kPoseRow + threadIdx.x] = tot[threadIdx.x];
   } else {
     GradsOut out{a};
     project_bwd_one<kHot>(a, g, sums, out);
+  }
+}
+
+// d_view[12] (fp32, rows [d_R | d_t]) from the partial rows: thread t sums rows
+// t, t + kBlock, ... in index order, then pose_block_sum's fixed tree; the SH
+// origin campos = -R^T t folds in as d_R[i][j] -= t[i] d_campos[j],
+// d_t[i] -= sum_j R[i][j] d_campos[j].  One workgroup.
+struct PoseView {
+  float v[12];
+};
+__global__ __launch_bounds__(kBlock) void k_pose_reduce(const double *partials, int64_t rows, PoseView view,
+                                                        float *d_view) {
+  __shared__ double red[kBlock / kWave][kPoseRow], tot[kPoseRow];
+  double acc[kPoseVals];
+#pragma unroll
+  for (int q = 0; q < kPoseVals; ++q) acc[q] = 0.0;
+  for (int64_t r = threadIdx.x; r < rows; r += kBlock) {
+#pragma unroll
+    for (int q = 0; q < kPoseVals; ++q) acc[q] += partials[r * kPoseRow + q];
+  }
+  pose_block_sum(acc, red, tot);
+  if (threadIdx.x < 12) {
+    const int i = threadIdx.x / 4, j = threadIdx.x % 4;
+    const float *R = view.v;
+    double x;
+    if (j < 3)
+      x = tot[i * 3 + j] - (double)R[i * 4 + 3] * tot[12 + j];
+    else
+      x = tot[9 + i] - ((double)R[i * 4] * tot[12] + (double)R[i * 4 + 1] * tot[13] + (double)R[i * 4 + 2] * tot[14]);
+    d_view[threadIdx.x] = (float)x;
   }
 }
 
@@ -2874,19 +2995,26 @@ gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, g
   return launch_gather(a, accumulate, (hipStream_t)stream);
 }
 
-gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) {
-  if (!a) return fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_project_backward");
-  if (a->g.n <= 0) return GS_OK;
+namespace {
+// the projection backward's argument checks (n > 0)
+gs_status check_project_bwd(const gs_project_bwd_args *a, const char *what) {
   const bool raw = a->g.cov3d == nullptr;
   if (!a->g.xyz || !a->g.color_logits || !a->means2d || !a->conics || !a->vis || !a->rects ||
       !a->pair_offset || !a->d_xyz || !a->d_color_logits || !a->d_opacity ||
       (raw ? (!a->g.scaling || !a->g.rotation || !a->d_scaling || !a->d_rotation) : !a->d_cov3d) ||
       (a->pair_grads && (!a->grad_sums || !a->slot_live || a->partial_groups < 1)))
-    return fail(GS_ERR_INVALID_ARG, "%s: null buffer", "gs_project_backward");
+    return fail(GS_ERR_INVALID_ARG, "%s: null buffer", what);
   if (a->g.sh_degree < 0 || a->g.sh_degree > 3 || (a->g.sh_degree > 0 && (!a->g.sh_rest || !a->d_sh_rest)))
-    return fail(GS_ERR_INVALID_ARG, "%s: sh_degree must be 0..3, with sh_rest and d_sh_rest when > 0",
-                "gs_project_backward");
-  if (a->pair_grads && !cam_ok(a->cam)) return fail(GS_ERR_UNSUPPORTED, kCamMsg, "gs_project_backward");
+    return fail(GS_ERR_INVALID_ARG, "%s: sh_degree must be 0..3, with sh_rest and d_sh_rest when > 0", what);
+  if (a->pair_grads && !cam_ok(a->cam)) return fail(GS_ERR_UNSUPPORTED, kCamMsg, what);
+  return GS_OK;
+}
+}  // namespace
+
+gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) {
+  if (!a) return fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_project_backward");
+  if (a->g.n <= 0) return GS_OK;
+  if (gs_status st = check_project_bwd(a, "gs_project_backward")) return st;
   hipStream_t s = (hipStream_t)stream;
   const bool hot = a->grad_sums && !a->g_means2d && !a->g_conics && !a->g.cov3d && a->g.sh_degree == 0 && !a->order;
   if (a->pair_grads) {  // (NULL with grad_sums: the sums are there already, gs_gather_partials)
@@ -2898,6 +3026,37 @@ gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) 
   else
     k_project_bwd<false><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a);
   return check_launch("gs_project_backward");
+}
+
+gs_status gs_project_backward_pose(const gs_project_pose_args *p, gs_stream_t stream) {
+  static const char *what = "gs_project_backward_pose";
+  if (!p) return fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  const gs_project_bwd_args *a = &p->bwd;
+  if (!p->d_view) return fail(GS_ERR_INVALID_ARG, "%s: null d_view", what);
+  if (a->order)
+    return fail(GS_ERR_UNSUPPORTED, "%s: the pose reduction walks the Gaussians in index order (order must be NULL)",
+                what);
+  hipStream_t s = (hipStream_t)stream;
+  if (a->g.n <= 0) {  // nothing to sum: a zero gradient
+    if (hipMemsetAsync(p->d_view, 0, 12 * sizeof(float), s) != hipSuccess)
+      return fail(GS_ERR_LAUNCH, "%s: d_view memset failed", what);
+    return GS_OK;
+  }
+  const int64_t blocks = div_up(a->g.n, kBlock);
+  if (!p->pose_partials) return fail(GS_ERR_INVALID_ARG, "%s: null pose_partials", what);
+  if (p->pose_partial_rows < blocks)
+    return fail(GS_ERR_INVALID_ARG, "%s: pose_partial_rows below ceil(n / 256), one row per workgroup", what);
+  if (gs_status st = check_project_bwd(a, what)) return st;
+  if (a->pair_grads) {
+    gs_status st = launch_gather(a, 0, s);
+    if (st) return st;
+  }
+  k_project_bwd<false, false, true><<<(unsigned)blocks, kBlock, 0, s>>>(*a, PoseArgs{p->pose_partials});
+  if (gs_status st = check_launch(what)) return st;
+  PoseView view;
+  memcpy(view.v, a->cam.view, sizeof(view.v));
+  k_pose_reduce<<<1, kBlock, 0, s>>>(p->pose_partials, blocks, view, p->d_view);
+  return check_launch(what);
 }
 
 gs_status gs_project_backward_adam(const gs_project_bwd_args *a, const gs_adam_args *adam, gs_stream_t stream) {

@@ -42,7 +42,7 @@ import torch
 
 from . import _native as N
 from . import rasterizer as RZ
-from .renderer import camera_params
+from .renderer import _world_view, camera_params
 
 HYPER_ROWS = 4096  # replays between two refills of the Adam hyper-parameter table (one sync each)
 
@@ -71,7 +71,13 @@ class GraphedStep:
                             f"{type(optimizer).__name__}")
         self.renderer, self.camera, self.model, self.settings, self.optimizer = (renderer, camera, model, settings,
                                                                                  optimizer)
-        self.cam = camera_params(camera, settings, renderer.radius_min, renderer.radius_max, renderer.tile_size)
+        wv = _world_view(camera)
+        if wv.requires_grad:
+            raise ValueError("GraphedStep does not compute camera-pose gradients: the camera's world_view_transform "
+                             "requires grad, and a replayed step's pose is fixed host scalars with no pose "
+                             "reduction in the graph -- render through GaussianRenderer.render, or detach the view")
+        self.cam = camera_params(camera, settings, renderer.radius_min, renderer.radius_max, renderer.tile_size,
+                                 world_view=wv)
         if self.cam.tile_size != N.GS_DEFAULT_TILE:
             raise ValueError("GraphedStep renders the default 16-px tile")
         sh = settings.sh_degree if settings.sh_degree is not None else int(getattr(model, "active_sh_degree", 0))

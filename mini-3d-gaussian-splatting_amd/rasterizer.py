@@ -799,9 +799,13 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
 def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotation, logits, opacity,
                       means2d, conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit=False,
-                      sh_rest=None, sh_degree=0, out=None, outputs=None):
+                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None):
     """outputs: the forward's (image, alpha, depth), unmodified -- with the
     frame's clamp flags they are the blend backward's per-pixel state.
+    d_view: optional fp32 [12] on the device -- the projection backward then
+    runs as gs_project_backward_pose, one range over every Gaussian, and
+    writes dL/d(view rows [R | t]) there (the per-Gaussian gradients are the
+    same bits either way).
     out: optional preallocated gradient tensors {name: tensor} (the
     data-parallel bucket's views, distributed.GradAllReduce.attach); the
     kernels write there instead of into fresh buffers.  out["_rows_ready"]
@@ -811,7 +815,7 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     if isinstance(fr, _FastFrame):
         return _backward_frame(cam, fr, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics, g_image,
                                g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
-                               outputs)
+                               outputs, d_view)
     lib = N.load()
     dev = xyz.device
     n = int(xyz.shape[0])
@@ -892,6 +896,12 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                             N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col), N.ptr(d_op), N.ptr(d_sh),
                             N.ptr(slot_live), N.ptr(grad_sums), fr.groups)
     StageTimer.mark("project_bwd")
+    if d_view is not None:
+        _project_backward_pose(lib, pb, n, d_view, s)
+        if rows_ready is not None:
+            rows_ready(0, n)
+        StageTimer.mark("~end_bwd")
+        return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
     bounds = [n * k // chunks for k in range(chunks + 1)]
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         part = pb if (lo, hi) == (0, n) else _rows_of(pb, lo, hi)
@@ -900,6 +910,16 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
             rows_ready(lo, hi)
     StageTimer.mark("~end_bwd")
     return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
+
+
+def _project_backward_pose(lib, pb: "N.GsProjectBwdArgs", n: int, d_view: torch.Tensor, s) -> None:
+    """gs_project_backward_pose over every Gaussian of `pb`: the projection
+    backward plus the deterministic two-level sum of the pose gradient (one
+    row of partials per workgroup of GS_POSE_BLOCK Gaussians)."""
+    rows = max(1, (n + N.GS_POSE_BLOCK - 1) // N.GS_POSE_BLOCK)
+    partials = torch.empty((rows, N.GS_POSE_ROW), dtype=torch.float64, device=d_view.device)
+    pa = N.GsProjectPoseArgs(pb, partials.data_ptr(), rows, d_view.data_ptr())
+    N.check(lib.gs_project_backward_pose(C.byref(pa), s), "gs_project_backward_pose")
 
 
 def _blend_outputs(outputs):
@@ -916,11 +936,11 @@ def _blend_outputs(outputs):
 
 def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rotation, logits, opacity, means2d,
                     conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
-                    outputs):
+                    outputs, d_view=None):
     """backward_pipeline through gs_render_backward (the frame of
     _forward_frame): the blend backward and the gather in the library, then
     the projection backward -- there too unless the data-parallel reduction
-    wants the rows in ranges."""
+    wants the rows in ranges, or the pose gradient is wanted (d_view)."""
     lib = N.load()
     dev = xyz.device
     n = int(xyz.shape[0])
@@ -966,12 +986,12 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     d_sh = buf("sh_rest", (n, N.GS_SH_REST, 3)) if sh_degree > 0 else None
     ba.d_xyz, ba.d_cov3d, ba.d_scaling, ba.d_rotation = N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot)
     ba.d_color_logits, ba.d_opacity, ba.d_sh_rest = N.ptr(d_col), N.ptr(d_op), N.ptr(d_sh)
-    ba.project = 1 if chunks == 1 else 0
+    ba.project = 1 if (chunks == 1 and d_view is None) else 0
     ev = StageTimer.pair("blend_bwd")
     if ev is not None:
         ba.blend_events[0], ba.blend_events[1] = ev[0].handle, ev[1].handle
     N.check(lib.gs_render_backward(C.byref(ba), s), "gs_render_backward")
-    if chunks == 1:
+    if chunks == 1 and d_view is None:
         if rows_ready is not None:
             rows_ready(0, n)
         return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
@@ -983,6 +1003,12 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
                             None, N.ptr(gm),
                             N.ptr(gc), N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col),
                             N.ptr(d_op), N.ptr(d_sh), None, ba.grad_sums if pair_grads is not None else None, 0)
+    if d_view is not None:
+        # one range over every Gaussian, with the pose gradient's reduction
+        _project_backward_pose(lib, pb, n, d_view, s)
+        if rows_ready is not None:
+            rows_ready(0, n)
+        return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
     bounds = [n * k // chunks for k in range(chunks + 1)]
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         N.check(lib.gs_project_backward(C.byref(_rows_of(pb, lo, hi)), s), "gs_project_backward")
@@ -1023,12 +1049,16 @@ class RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None):
+        # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
+        # Gaussians' device, given only to receive its gradient -- the forward
+        # reads the pose from `cam`, whose values are the same
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]))
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
+        ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[11] else None
         # (the outputs image / alpha / depth too: the blend backward's per-pixel
         # state; autograd refuses the backward if they were modified in place)
         ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
@@ -1042,11 +1072,19 @@ class RasterizeGaussians(torch.autograd.Function):
         xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth = ctx.saved_tensors
         g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
         dest = ctx.grad_dest() if ctx.grad_dest is not None else None
+        d_view = None
+        if ctx.view_shape is not None:
+            d_view = torch.empty((12,), dtype=torch.float32, device=xyz.device)
         d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, None if g_alpha is None else g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
-            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth))
+            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view)
         need = ctx.needs_input_grad
+        g_view = None
+        if d_view is not None:
+            g_view = d_view.view(3, 4)
+            if ctx.view_shape == (4, 4):
+                g_view = torch.cat([g_view, g_view.new_zeros((1, 4))], 0)
         return (d_xyz if need[0] else None,
                 d_cov if (cov3d is not None and need[1]) else None,
                 d_scl if (scaling is not None and need[2]) else None,
@@ -1054,11 +1092,11 @@ class RasterizeGaussians(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                None, None, None, None)
+                None, None, None, None, g_view)
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
-              sh_rest=None, sh_degree=0, grad_dest=None):
+              sh_rest=None, sh_degree=0, grad_dest=None, view=None):
     """opacity_is_logit: opacity holds the model's raw _opacity and the kernels
     apply get_opacity's sigmoid (fused; its gradient goes to the logit).
     sh_degree > 0: view-dependent colour from sh_rest ([N,15,3] rest
@@ -1066,7 +1104,11 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     colour (include/gsplat_mi355x.h, gs_gaussians).
     grad_dest: optional callable, asked at backward time, returning None or
     {name: tensor} buffers the gradient kernels write into (names xyz,
-    scaling, rotation, color, opacity, sh_rest; see backward_pipeline)."""
+    scaling, rotation, color, opacity, sh_rest; see backward_pipeline).
+    view: optional [3,4] or [4,4] floating-point tensor, the world-to-camera
+    matrix whose rows cam.view holds, on any device: when it requires grad it
+    receives dL/d(view) (in its own dtype, on its own device; row 3 of a 4x4
+    is zero).  The forward's values come from `cam` either way."""
     _check_inputs(xyz)
     n = int(xyz.shape[0]) if xyz.dim() == 2 else -1
     if n < 0 or xyz.shape[1] != 3:
@@ -1115,5 +1157,13 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     xyz, _ = _rows(xyz, 3)
     logits, _ = _rows(logits, 3)
     opacity, _ = _rows(opacity, 1)
+    if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
+        return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
+                                        bool(opacity_is_logit), sh_degree, grad_dest)
+    if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
+        raise ValueError(f"view must be a floating-point [3,4] or [4,4] tensor, got {view.dtype} {tuple(view.shape)}")
+    # (differentiable, as the reference's .to(device): the gradient returns to
+    # the caller's device and dtype)
+    view = view.to(device=xyz.device, dtype=torch.float32)
     return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                    bool(opacity_is_logit), sh_degree, grad_dest)
+                                    bool(opacity_is_logit), sh_degree, grad_dest, view)

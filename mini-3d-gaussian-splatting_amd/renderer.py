@@ -19,6 +19,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     same leaves, except `_features_rest`, whose gradient is identically zero
     in the reference and is left as None here.
   * `radii` and `visibility_filter` carry no gradient.
+  * A `world_view_transform` that requires grad receives its gradient, as in
+    the reference (pose refinement: pose.CameraPose); with torch.no_grad or a
+    plain tensor nothing about the render changes.
   * `settings.scale_modifier` and `settings.debug` are ignored, as in the
     reference.
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
@@ -91,12 +94,15 @@ def _host_f32(t, count: int) -> list:
     return t.reshape(count).tolist()
 
 
-def camera_params(camera, settings: RenderSettings, radius_min=0.01, radius_max=50.0, tile_size=16) -> CameraParams:
-    """Host scalars of renderer.py:140-152 (python double -> fp32 in the ABI)."""
+def camera_params(camera, settings: RenderSettings, radius_min=0.01, radius_max=50.0, tile_size=16,
+                  world_view=None) -> CameraParams:
+    """Host scalars of renderer.py:140-152 (python double -> fp32 in the ABI).
+    world_view: the camera's world_view_transform when the caller has read it
+    already."""
     W, H = camera._width, camera._height
     fx = 0.5 * W / math.tan(camera._FoVx * 0.5)
     fy = 0.5 * H / math.tan(camera._FoVy * 0.5)
-    view = tuple(_host_f32(_world_view(camera), 16)[:12])
+    view = tuple(_host_f32(_world_view(camera) if world_view is None else world_view, 16)[:12])
     bg = tuple(_host_f32(settings.bg_color, 3))
     tile = effective_tile(tile_size, settings.image_width, settings.image_height)
     return CameraParams(int(settings.image_width), int(settings.image_height), fx, fy, W * 0.5, H * 0.5,
@@ -121,7 +127,12 @@ class GaussianRenderer:
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
     def render(self, camera, gaussians, settings: RenderSettings) -> Dict[str, torch.Tensor]:
-        cam = camera_params(camera, settings, self.radius_min, self.radius_max, self.tile_size)
+        wv = _world_view(camera)
+        cam = camera_params(camera, settings, self.radius_min, self.radius_max, self.tile_size, world_view=wv)
+        # a view on the autograd tape receives its gradient (the reference's
+        # autograd reaches world_view_transform(), renderer.py:150-168); any
+        # other view is host scalars only, as before
+        pose = {"view": wv} if wv.requires_grad else {}
         xyz = gaussians.get_xyz
         fused = getattr(gaussians, "_gs_fused_covariance", False)
         if fused:
@@ -173,7 +184,7 @@ class GaussianRenderer:
                 return d
         image, alpha, depth, means2d, conics, radii, vis = rasterize(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
-            sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest)
+            sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **pose)
         # the reference's output dtypes (renderer.py:74-83, :273-275, :359-367):
         # the projection outputs in the Gaussians' dtype, image in the
         # background's (out_rgb starts as bg), alpha / depth float32 (zeros of
