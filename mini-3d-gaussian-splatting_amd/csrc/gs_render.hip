@@ -19,10 +19,6 @@
 #include "gs_internal.h"
 #include "gsplat_mi355x.h"
 
-#ifndef GS_EMIT_TILE_HIST
-#define GS_EMIT_TILE_HIST 0
-#endif
-
 namespace {
 
 size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -242,15 +238,10 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
   ba.capacity = a->fb.capacity;
   ba.tile_keys = a->fb.capacity > 0 ? reinterpret_cast<uint32_t *>(tw + T0.tk[0]) : nullptr;
   ba.pair_gauss = a->fb.capacity > 0 ? reinterpret_cast<uint32_t *>(tw + T0.tv[0]) : nullptr;
-  // GS_EMIT_TILE_HIST=1 (a variant, off): the tile sort's first-pass digit
-  // counts come from the emission (the count clears their table in the tile
-  // sort's workspace), one histogram kernel less.  Measured at C3: the
-  // emission took 23 -> 36 us against the 5.7 us histogram kernel it saves
-  // (DESIGN.md section 4), so the product keeps the separate histogram.
+  // (the tile sort counts its own first-pass digits: counting them in the
+  // emission took that kernel 23 -> 36 us at C3 against the 5.7 us histogram
+  // kernel it saved)
   const int32_t bits = tiles > 1 ? 32 - __builtin_clz((uint32_t)(tiles - 1)) : 1;
-  const int32_t bits0 = gs_internal_first_pass_bits(0, bits);
-  uint32_t *tile_counts =
-      (GS_EMIT_TILE_HIST && a->fb.capacity > 0 && !dev) ? reinterpret_cast<uint32_t *>(tw + T0.sort_ws) : nullptr;
   if (dev) {
     // the count (status and T_eff on the device), the emission into the
     // capacity (skipped by the kernel when T exceeds it), and on: no wait
@@ -266,10 +257,8 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
     ba.host_seq = a->host_seq;
     volatile uint32_t *hc = a->host_counters_host;
     hc[4] = 0u;  // (the previous frame's sequence word)
-    if ((st = gs_internal_bin_count_hist(&ba, tile_counts, bits0, stream))) return st;
-    if (a->fb.capacity > 0 &&
-        (st = tile_counts ? gs_internal_bin_emit_hist(&ba, tile_counts, bits0, stream) : gs_bin_emit(&ba, stream)))
-      return st;
+    if ((st = gs_bin_count(&ba, stream))) return st;
+    if (a->fb.capacity > 0 && (st = gs_bin_emit(&ba, stream))) return st;
     // the one host synchronisation of a frame: poll the sequence word the
     // count writes through the pinned buffer's device address (no event, no copy)
     // After 10 s of polling the stream is synchronised and the word read once
@@ -302,13 +291,7 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
   } else {
     if ((int64_t)a->T > a->fb.capacity)
       return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: resume needs a capacity of at least T", what);
-    if (tile_counts) {
-      const size_t words = ((size_t)1 << bits0) * (((size_t)a->fb.capacity + kSortBlockEntries - 1) / kSortBlockEntries);
-      if (hipMemsetAsync(tile_counts, 0, 4 * words, (hipStream_t)stream) != hipSuccess)
-        return gs_internal_fail(GS_ERR_LAUNCH, "%s: count table memset failed", what);
-    }
-    if ((st = tile_counts ? gs_internal_bin_emit_hist(&ba, tile_counts, bits0, stream) : gs_bin_emit(&ba, stream)))
-      return st;
+    if ((st = gs_bin_emit(&ba, stream))) return st;
   }
   // the entries the launches are sized for: T, or the capacity with the
   // kernels reading T_eff (counters[5]: T, 0 for a failed frame) themselves
@@ -318,12 +301,12 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
   uint32_t *tk = reinterpret_cast<uint32_t *>(tw + T0.tk[0]), *tk1 = reinterpret_cast<uint32_t *>(tw + T0.tk[1]);
   uint32_t *tv = reinterpret_cast<uint32_t *>(tw + T0.tv[0]), *tv1 = reinterpret_cast<uint32_t *>(tw + T0.tv[1]);
   // (the one-workgroup sort and the radix passes are both stable: one order)
-  if (T <= gs_internal_small_sort_max() && !tile_counts) {
+  if (T <= gs_internal_small_sort_max()) {
     if ((st = gs_internal_small_sort(tk, tv, tk1, tv1, T, bits, t_dev, stream))) return st;
     talt = 1;
   } else if ((st = gs_internal_radix_sort_pairs(tk, tv, tk1, tv1, T, 0, bits, 0, tw + T0.sort_ws,
-                                                gs_radix_sort_workspace_bytes((int32_t)a->fb.capacity), &talt,
-                                                GS_EMIT_TILE_HIST ? 1 : 0, t_dev, stream))) {
+                                                gs_radix_sort_workspace_bytes((int32_t)a->fb.capacity), &talt, t_dev,
+                                                stream))) {
     return st;
   }
   a->tile_alt = talt;

@@ -36,7 +36,6 @@ constexpr int kRadix = 1 << kRadixBits;
 #endif
 constexpr int kSortIpt = GS_SORT_IPT;            // items per thread per sort block (4, 16: slower)
 constexpr int kSortChunk = kBlock * kSortIpt;    // 2048 items per block
-static_assert(kSortChunk == kSortBlockEntries, "gs_internal.h kSortBlockEntries");
 constexpr int kBinChunk = kBlock * 4;            // 1024 Gaussians per binning block (2 and 1 rounds: slower)
 #ifndef GS_DEBUG  // 1: report (printf) blend list ranges clamped to the T entries
 #define GS_DEBUG 0
@@ -823,18 +822,8 @@ __device__ __forceinline__ uint2 *sorted_rects(uint32_t *partials, int nb) {
 
 // partials[0..nb): touches per block (depth order), partials[nb..2nb): visible per index chunk,
 // [2nb..3nb): index-order slots per chunk, [3nb..5nb): depth-bits min / max per chunk
-// The tile sort's first-pass digit counts (k_radix_hist's table), built by
-// k_bin_emit as it writes the entries (gs_internal_bin_emit_hist): the
-// table, zeroed by k_bin_partials, the kernel before it in the stream.
-struct TileHist {
-  uint32_t *counts;     // [2^bits, nb_sort] (row d: digit d's count per sort block)
-  uint32_t zero_words;  // words k_bin_partials clears: 2^bits * div_up(capacity, kSortChunk)
-  int bits;             // first pass digit width (shift 0); 0: no table
-};
-
-__global__ __launch_bounds__(kBlock) void k_bin_partials(gs_bin_args a, uint32_t *partials, int nb, TileHist th) {
+__global__ __launch_bounds__(kBlock) void k_bin_partials(gs_bin_args a, uint32_t *partials, int nb) {
   __shared__ uint32_t s_tmp3[3][kBlock / kWave];
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < th.zero_words; i += gridDim.x * kBlock) th.counts[i] = 0u;
   const long long base = (long long)blockIdx.x * kBinChunk;
   constexpr int kR = kBinChunk / kBlock;
   // Loads unconditional (clamped index) and all rounds' at once: two round
@@ -1066,24 +1055,13 @@ __device__ __forceinline__ void wave_fill_runs(bool wide, uint32_t lo, uint32_t 
 }
 
 constexpr uint32_t kOwnerCap = kBlock * 64;
-// sort blocks a binning block's output may span with its digit counts in LDS
-// (a block emits ~4.5 K entries at C3, ~3 sort blocks); counts past them go
-// straight to the table
-#ifndef GS_HIST_SPAN
-#define GS_HIST_SPAN 8
-#endif
-constexpr int kHistSpan = GS_HIST_SPAN;
-// kHist: the fused first-pass histogram (GS_EMIT_TILE_HIST, off); the product
-// instantiation carries neither its LDS table nor its registers
-template <bool kHist>
-__global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32_t *partials, TileHist th) {
+__global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32_t *partials) {
   __shared__ uint32_t s_off[kBlock + 1];
   __shared__ uint32_t s_g[kBlock];
   __shared__ uint2 s_rect[kBlock];
   __shared__ uint32_t s_tmp[4];
   __shared__ uint32_t s_tmp3[3][kBlock / kWave];
   __shared__ uint8_t s_owner[kOwnerCap];
-  __shared__ uint32_t s_hist[kHist ? kHistSpan * kRadix : 1];
   const long long base = (long long)blockIdx.x * kBinChunk;
   // a device-resident frame that failed (gs_bin_count's status): no entry is
   // emitted and every rectangle of the chunk is cleared, so the frame's
@@ -1101,15 +1079,6 @@ __global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32
   const uint32_t T = a.counters[1];
   if ((long long)T > a.capacity) return;
   uint32_t out_base = partials[blockIdx.x];
-  // first-pass digit counts of the entries this block writes: sort block
-  // (out_base + o) / kSortChunk, digit key & hmask (shift 0)
-  const bool hist = kHist && th.bits > 0;
-  const uint32_t hmask = (1u << th.bits) - 1u, nbs = (T + kSortChunk - 1) / kSortChunk;
-  const uint32_t hb0 = out_base / kSortChunk;
-  if (hist) {
-    for (int i = threadIdx.x; i < kHistSpan * kRadix; i += kBlock) s_hist[i] = 0u;
-    // (ordered before the first use by the barriers inside the prefix scans)
-  }
   constexpr int kR = kBinChunk / kBlock;
   // all rounds' ids and rects unconditionally (clamped): one round trip for
   // the block
@@ -1179,24 +1148,9 @@ __global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32
         const uint32_t key = (ty0 + row) * (uint32_t)a.tiles_x + tx0 + (loc - row * wt);
         a.tile_keys[out_base + o] = key;
         a.pair_gauss[out_base + o] = s_g[lo];
-        if (hist) {
-          const uint32_t sb = (out_base + o) / kSortChunk, d = key & hmask;
-          if (sb - hb0 < (uint32_t)kHistSpan)
-            atomicAdd(&s_hist[(sb - hb0) * kRadix + d], 1u);
-          else
-            atomicAdd(&th.counts[(size_t)d * nbs + sb], 1u);
-        }
       }
     }
     out_base += tot;
-  }
-  if (hist) {
-    __syncthreads();
-    // (integer sums: the table is the same whatever order the blocks add in)
-    for (int i = threadIdx.x; i < kHistSpan * kRadix; i += kBlock) {
-      const uint32_t v = s_hist[i], sb = hb0 + (uint32_t)(i / kRadix), d = (uint32_t)(i % kRadix);
-      if (v && sb < nbs && d <= hmask) atomicAdd(&th.counts[(size_t)d * nbs + sb], v);
-    }
   }
   // Gradient slots, in Gaussian-index order over this block's index chunk
   // (coalesced): the chunk's offset + each Gaussian's prefix in the chunk
@@ -2704,7 +2658,7 @@ gs_status gs_radix_sort_pairs(uint32_t *keys, uint32_t *vals, uint32_t *keys_alt
                               void *workspace, size_t workspace_bytes, int32_t *result_in_alt,
                               gs_stream_t stream) {
   return gs_internal_radix_sort_pairs(keys, vals, keys_alt, vals_alt, n, begin_bit, end_bit, vals_are_iota,
-                                      workspace, workspace_bytes, result_in_alt, 0, nullptr, stream);
+                                      workspace, workspace_bytes, result_in_alt, nullptr, stream);
 }
 
 }  // extern "C"
@@ -2712,7 +2666,7 @@ gs_status gs_radix_sort_pairs(uint32_t *keys, uint32_t *vals, uint32_t *keys_alt
 gs_status gs_internal_radix_sort_pairs(uint32_t *keys, uint32_t *vals, uint32_t *keys_alt, uint32_t *vals_alt,
                                        int32_t n, int32_t begin_bit, int32_t end_bit, int32_t vals_are_iota,
                                        void *workspace, size_t workspace_bytes, int32_t *result_in_alt,
-                                       int32_t first_counts_ready, const uint32_t *n_dev, gs_stream_t stream) {
+                                       const uint32_t *n_dev, gs_stream_t stream) {
   if (!result_in_alt) return fail(GS_ERR_INVALID_ARG, "%s: null result_in_alt", "gs_radix_sort_pairs");
   if (begin_bit < 0 || end_bit > 32 || begin_bit >= end_bit || n < 0)
     return fail(GS_ERR_INVALID_ARG, "%s: bad bit range / n", "gs_radix_sort_pairs");
@@ -2735,7 +2689,7 @@ gs_status gs_internal_radix_sort_pairs(uint32_t *keys, uint32_t *vals, uint32_t 
   int shift = begin_bit;
   for (int p = 0; p < passes; ++p) {
     const int nbits = (end_bit - shift) / (passes - p);
-    if (p > 0 || !first_counts_ready) k_radix_hist<<<nb, kBlock, 0, s>>>(kin, n, shift, nbits, counts, nb, n_dev);
+    k_radix_hist<<<nb, kBlock, 0, s>>>(kin, n, shift, nbits, counts, nb, n_dev);
     k_radix_scan<<<1 << nbits, kBlock, 0, s>>>(counts, totals, nb, n_dev);
     if (p == 0 && vals_are_iota)
       k_radix_scatter<true><<<nb, kBlock, 0, s>>>(kin, nullptr, kout, vout, n, shift, nbits, counts, totals, nb,
@@ -2766,33 +2720,6 @@ gs_status gs_internal_small_sort(const uint32_t *keys, const uint32_t *vals, uin
       const_cast<uint32_t *>(keys), const_cast<uint32_t *>(vals), nullptr, bits, nullptr, (uint32_t)n, keys_out,
       vals_out, n_dev);
   return check_launch("gs_internal_small_sort");
-}
-
-int32_t gs_internal_first_pass_bits(int32_t begin_bit, int32_t end_bit) {
-  const int passes = (end_bit - begin_bit + kRadixBits - 1) / kRadixBits;
-  return passes > 0 ? (end_bit - begin_bit) / passes : 0;  // (the narrower digit first, as the sort)
-}
-
-gs_status gs_internal_bin_count_hist(const gs_bin_args *a, uint32_t *tile_counts, int32_t bits, gs_stream_t stream) {
-  if (!a || !a->counters || a->n <= 0 || !a->workspace || a->workspace_bytes < gs_bin_workspace_bytes(a->n))
-    return fail(GS_ERR_INVALID_ARG, "%s: bad args", "gs_internal_bin_count_hist");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)div_up(a->n, kBinChunk);
-  uint32_t *partials = (uint32_t *)a->workspace;
-  const uint32_t zero = tile_counts ? (uint32_t)((1u << bits) * div_up(a->capacity > 0 ? a->capacity : 0, kSortChunk))
-                                    : 0u;
-  k_bin_partials<<<nb, kBlock, 0, s>>>(*a, partials, nb, TileHist{tile_counts, zero, 0});
-  k_bin_scan_partials<<<1, kBlock, 0, s>>>(*a, partials, nb);
-  return check_launch("gs_bin_count");
-}
-
-gs_status gs_internal_bin_emit_hist(const gs_bin_args *a, uint32_t *tile_counts, int32_t bits, gs_stream_t stream) {
-  if (!a || a->n <= 0 || !tile_counts || bits < 1 || bits > kRadixBits)
-    return fail(GS_ERR_INVALID_ARG, "%s: bad args", "gs_internal_bin_emit_hist");
-  hipStream_t s = (hipStream_t)stream;
-  const int nb = (int)div_up(a->n, kBinChunk);
-  k_bin_emit<true><<<nb, kBlock, 0, s>>>(*a, (const uint32_t *)a->workspace, TileHist{tile_counts, 0u, bits});
-  return check_launch("gs_bin_emit");
 }
 
 extern "C" {
@@ -2835,7 +2762,7 @@ gs_status gs_bin_count(const gs_bin_args *a, gs_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   const int nb = (int)div_up(a->n, kBinChunk);
   uint32_t *partials = (uint32_t *)a->workspace;
-  k_bin_partials<<<nb, kBlock, 0, s>>>(*a, partials, nb, TileHist{nullptr, 0u, 0});
+  k_bin_partials<<<nb, kBlock, 0, s>>>(*a, partials, nb);
   k_bin_scan_partials<<<1, kBlock, 0, s>>>(*a, partials, nb);
   return check_launch("gs_bin_count");
 }
@@ -2851,7 +2778,7 @@ gs_status gs_bin_emit(const gs_bin_args *a, gs_stream_t stream) {
   if (a->capacity < 0) return fail(GS_ERR_INVALID_ARG, "%s: negative capacity", "gs_bin_emit");
   hipStream_t s = (hipStream_t)stream;
   const int nb = (int)div_up(a->n, kBinChunk);
-  k_bin_emit<false><<<nb, kBlock, 0, s>>>(*a, (const uint32_t *)a->workspace, TileHist{nullptr, 0u, 0});
+  k_bin_emit<<<nb, kBlock, 0, s>>>(*a, (const uint32_t *)a->workspace);
   return check_launch("gs_bin_emit");
 }
 

@@ -205,30 +205,22 @@ class GraphedStep:
         """Buffers for this capacity and window, the argument structs, and the graph."""
         lib, cam, dev = self.lib, self.cam, self.dev
         tiles, cells, groups = cam.tiles_x * cam.tiles_y, cam.cells, cam.groups
-        seen = RZ._T_SEEN.get(dev, 0)
-        cap = self.capacity if self.capacity is not None else max(seen + seen // 4 + 4096, 4096)
+        cap = self.capacity if self.capacity is not None else RZ._capacity_guess(dev) or 4096
         if self.tile_ws is None or self._cap != cap:
             tws = int(lib.gs_tile_workspace_bytes(cap, tiles, cells, groups))
             self.tile_ws = torch.empty((tws,), dtype=torch.uint8, device=dev)
             self.pair_grads = torch.empty((cap * groups, N.GS_PARTIAL_STRIDE), dtype=torch.float32, device=dev)
-            self._cap, self._tws = cap, tws
-        window = RZ._window_for(dev) if self.window == "auto" else self.window
+            self._cap = cap
         m = self.model
         fa = N.GsRenderFwdArgs()
-        fa.cam = cam.to_struct()
-        fa.g = RZ._build_gaussians_struct(self.n, m._xyz, None, m._scaling, m._rotation, m._features_dc,
-                                          m._opacity, opacity_is_logit=True)
-        fa.means2d, fa.conics, fa.radii, fa.vis = (self.means2d.data_ptr(), self.conics.data_ptr(),
-                                                   self.radii.data_ptr(), self.vis.data_ptr())
-        fa.image, fa.alpha, fa.depth = self.image.data_ptr(), self.alpha.data_ptr(), self.depth.data_ptr()
-        fb = fa.fb
-        fb.frame_ws, fb.frame_ws_bytes = self.frame_ws.data_ptr(), self.frame_ws.numel()
-        fb.tile_ws, fb.tile_ws_bytes, fb.capacity = self.tile_ws.data_ptr(), self._tws, cap
-        fb.live_cells, fb.flag_groups = cells, groups
-        fa.key_base, fa.key_bits = window if window is not None else (0, 32)
-        backoff = RZ._MSD_BACKOFF.get(dev, 0)
-        fa.depth_sort_msd = 1 if (RZ._DEPTH_MSD and window is not None and 9 <= fa.key_bits <= 31
-                                  and not backoff) else 0
+        RZ._bind_frame_args(fa, cam, RZ._build_gaussians_struct(self.n, m._xyz, None, m._scaling, m._rotation,
+                                                                m._features_dc, m._opacity, opacity_is_logit=True),
+                            (self.means2d, self.conics, self.radii, self.vis), (self.image, self.alpha, self.depth),
+                            self.frame_ws)
+        RZ._bind_tile_ws(fa, self.tile_ws, cap)
+        # (a capture looks at the MSD backoff; only rendered frames count it down)
+        window, fa.key_base, fa.key_bits, msd = RZ._depth_keys(dev, True, consume=False, window=self.window)
+        fa.depth_sort_msd = 1 if msd else 0
         fa.zero_slot_flags = 1
         fa.host_counters_dev, fa.host_counters_host = self.hc_dev, self.hc.data_ptr()
         fa.device_counts = 1

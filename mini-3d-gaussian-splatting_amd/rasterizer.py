@@ -298,12 +298,16 @@ class _HostCounters:
         self.dptr = N.host_device_pointer(self.t)
         self.seq = 0
 
+    def next_seq(self) -> int:
+        """This frame's sequence word (1 .. 2^31 - 1, never the cleared 0)."""
+        self.seq = self.seq % 0x7FFFFFFF + 1
+        return self.seq
+
     def arm(self, ba) -> None:
         if self.dptr is None:
             return
-        self.seq = self.seq % 0x7FFFFFFF + 1
         self.np[4] = 0  # (the previous frame's word; the GPU writes this frame's after its counters)
-        ba.host_counters, ba.host_seq = self.dptr, self.seq
+        ba.host_counters, ba.host_seq = self.dptr, self.next_seq()
 
     def wait(self, dev, ready) -> Tuple[int, int, int, int]:
         if self.dptr is None:
@@ -421,6 +425,50 @@ def window_holds(window, zmin_bits: int, zmax_bits: int) -> bool:
     return zmin_bits >= base and zmax_bits - base < _msd_limit(bits)
 
 
+# The per-frame decisions every host path takes from the state above (the
+# stage path, the frame entry points, graph_step.GraphedStep's capture).
+
+def _capacity_guess(dev) -> int:
+    """Tile entries to make room for before this device's next T is known:
+    its last frame's T and a quarter, plus 4096; 0 when no frame was seen."""
+    seen = _T_SEEN.get(dev, 0)
+    return seen + seen // 4 + 4096 if seen else 0
+
+
+def _depth_keys(dev, depth_window_ok: bool, consume: bool = True, window="auto"):
+    """(window, key_base, key_bits, msd) of this device's next depth sort: the
+    window of _window_for (none without depth_window_ok, or the caller's own),
+    32-bit keys without one, and whether gs_depth_sort_msd sorts them.  The MSD
+    backoff counts only frames that would have taken the MSD sort (it is per
+    process and device, not per host thread); a capture (consume=False) looks
+    at it without spending a frame of it."""
+    if window == "auto":
+        window = _window_for(dev) if depth_window_ok else None
+    key_base, key_bits = window if window is not None else (0, 32)
+    msd = _DEPTH_MSD and window is not None and 9 <= key_bits <= 31
+    backoff = _MSD_BACKOFF.get(dev, 0)
+    if msd and backoff and consume:
+        _MSD_BACKOFF[dev] = backoff - 1
+    return window, key_base, key_bits, bool(msd and not backoff)
+
+
+def _frame_missed(dev, depth_max_bits: int, T: int) -> None:
+    """A frame to render again with 32-bit keys: a visible depth outside the
+    window (the sort's keys were clipped), or an MSD bucket over capacity (the
+    depth max poisoned)."""
+    if depth_max_bits == _POISON:
+        _MSD_BACKOFF[dev] = _MSD_BACKOFF_FRAMES
+    else:
+        _note_window_miss(dev)
+    _T_SEEN[dev] = T
+
+
+def _frame_done(dev, T: int, zmin_bits: int, zmax_bits: int) -> None:
+    """A finished frame's T and visible depth range: the next frame's guesses."""
+    _T_SEEN[dev] = T
+    _record_depths(dev, zmin_bits, zmax_bits)
+
+
 def _alloc_tile_buffers(lib, cap: int, num_tiles: int, cam: CameraParams, dev):
     """One byte buffer for T <= cap entries: tile keys + Gaussian ids
     (ping-pong, 16 B/entry), the tile sort's workspace, the liveness bitmap
@@ -523,6 +571,45 @@ def _host_counters(dev) -> "_HostCounters":
     return hc
 
 
+def _gaussian_outputs(n: int, dev):
+    """A forward's per-Gaussian outputs: means2d, conics, radii, vis."""
+    f32 = torch.float32
+    return (torch.empty((n, 2), dtype=f32, device=dev), torch.empty((n, 2, 2), dtype=f32, device=dev),
+            torch.empty((n,), dtype=f32, device=dev), torch.empty((n,), dtype=torch.bool, device=dev))
+
+
+def _pixel_outputs(H: int, W: int, dev):
+    """A forward's per-pixel outputs: image, alpha, depth."""
+    f32 = torch.float32
+    return (torch.empty((3, H, W), dtype=f32, device=dev), torch.empty((1, H, W), dtype=f32, device=dev),
+            torch.empty((1, H, W), dtype=f32, device=dev))
+
+
+def _empty_frame_outputs(cam: CameraParams, dev):
+    """image, alpha, depth of a frame that draws nothing (M == 0).
+    renderer.py:74-83: bg once (not doubled, not clamped), zero alpha/depth"""
+    H, W, f32 = int(cam.image_height), int(cam.image_width), torch.float32
+    image = torch.tensor(cam.bg, dtype=f32, device=dev).view(3, 1, 1).repeat(1, H, W)
+    return image, torch.zeros((1, H, W), dtype=f32, device=dev), torch.zeros((1, H, W), dtype=f32, device=dev)
+
+
+def _bind_frame_args(fa: "N.GsRenderFwdArgs", cam: CameraParams, gst, gaussian_outs, pixel_outs, frame_ws) -> None:
+    """The fields of gs_render_forward's arguments every caller fills alike:
+    camera, Gaussians, the seven outputs and the frame workspace."""
+    fa.cam, fa.g = cam.to_struct(), gst
+    fa.means2d, fa.conics, fa.radii, fa.vis = (t.data_ptr() for t in gaussian_outs)
+    fa.image, fa.alpha, fa.depth = (t.data_ptr() for t in pixel_outs)
+    fb = fa.fb
+    fb.frame_ws, fb.frame_ws_bytes = frame_ws.data_ptr(), frame_ws.numel()
+    fb.live_cells, fb.flag_groups = cam.cells, cam.groups
+
+
+def _bind_tile_ws(fa: "N.GsRenderFwdArgs", tile_ws, cap: int) -> None:
+    """A tile workspace of gs_tile_workspace_bytes(cap, ...) bytes for `cap` entries."""
+    fb = fa.fb
+    fb.tile_ws, fb.tile_ws_bytes, fb.capacity = tile_ws.data_ptr(), tile_ws.numel(), cap
+
+
 def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest,
                    sh_degree, pair_counts, depth_window_ok, need_grad, hc, pix_neval):
     """forward_pipeline through gs_render_forward (the default tile)."""
@@ -530,7 +617,6 @@ def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opa
     dev = xyz.device
     n = int(xyz.shape[0])
     H, W = int(cam.image_height), int(cam.image_width)
-    f32 = torch.float32
     s = _stream()
     tiles = cam.tiles_x * cam.tiles_y
     key = (n, W, H, cam.tile_size)
@@ -538,74 +624,46 @@ def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opa
     if fws is None:
         fws = _WS_BYTES[key] = int(lib.gs_frame_workspace_bytes(n, W, H, cam.tile_size))
     fa = N.GsRenderFwdArgs()
-    fa.cam = cam.to_struct()
-    fa.g = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
-    means2d = torch.empty((n, 2), dtype=f32, device=dev)
-    conics = torch.empty((n, 2, 2), dtype=f32, device=dev)
-    radii = torch.empty((n,), dtype=f32, device=dev)
-    vis = torch.empty((n,), dtype=torch.bool, device=dev)
-    image = torch.empty((3, H, W), dtype=f32, device=dev)
-    alpha = torch.empty((1, H, W), dtype=f32, device=dev)
-    depth = torch.empty((1, H, W), dtype=f32, device=dev)
+    means2d, conics, radii, vis = gaussian_outs = _gaussian_outputs(n, dev)
+    image, alpha, depth = pixel_outs = _pixel_outputs(H, W, dev)
     frame_ws = torch.empty((fws,), dtype=torch.uint8, device=dev)
-    fa.means2d, fa.conics, fa.radii, fa.vis = (means2d.data_ptr(), conics.data_ptr(), radii.data_ptr(),
-                                               vis.data_ptr())
-    fa.image, fa.alpha, fa.depth = image.data_ptr(), alpha.data_ptr(), depth.data_ptr()
-    fb = fa.fb
-    fb.frame_ws, fb.frame_ws_bytes = frame_ws.data_ptr(), fws
-    fb.live_cells, fb.flag_groups = cam.cells, cam.groups
-    cap = _T_SEEN.get(dev, 0)
-    cap = cap + cap // 4 + 4096 if cap else 0
-    tile_ws = None
-    if cap:
+    _bind_frame_args(fa, cam, _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit,
+                                                sh_rest, sh_degree), gaussian_outs, pixel_outs, frame_ws)
+
+    def tile_workspace(cap):
         tws = int(lib.gs_tile_workspace_bytes(cap, tiles, cam.cells, cam.groups))
-        tile_ws = torch.empty((tws,), dtype=torch.uint8, device=dev)
-        fb.tile_ws, fb.tile_ws_bytes, fb.capacity = tile_ws.data_ptr(), tws, cap
-    window = _window_for(dev) if depth_window_ok else None
-    fa.key_base, fa.key_bits = window if window is not None else (0, 32)
-    msd = _DEPTH_MSD and window is not None and 9 <= fa.key_bits <= 31
-    backoff = _MSD_BACKOFF.get(dev, 0)
-    if msd and backoff:
-        _MSD_BACKOFF[dev] = backoff - 1
-    fa.depth_sort_msd = 1 if (msd and not backoff) else 0
+        ws = torch.empty((tws,), dtype=torch.uint8, device=dev)
+        _bind_tile_ws(fa, ws, cap)
+        return ws
+    cap = _capacity_guess(dev)
+    tile_ws = tile_workspace(cap) if cap else None
+    _, fa.key_base, fa.key_bits, msd = _depth_keys(dev, depth_window_ok)
+    fa.depth_sort_msd = 1 if msd else 0
     fa.zero_slot_flags = 1 if need_grad else 0
-    hc.seq = hc.seq % 0x7FFFFFFF + 1
-    fa.host_counters_dev, fa.host_counters_host, fa.host_seq = hc.dptr, hc.t.data_ptr(), hc.seq
+    fa.host_counters_dev, fa.host_counters_host, fa.host_seq = hc.dptr, hc.t.data_ptr(), hc.next_seq()
     fa.pair_counts, fa.pix_neval = N.ptr(pair_counts), N.ptr(pix_neval)
     fa.poll_timeout_ms = _POLL_TIMEOUT_MS
     st = lib.gs_render_forward(C.byref(fa), s)
     if st == N.GS_RETRY_FULL_KEYS:
-        # a visible depth outside the window, or an MSD bucket over capacity
-        if fa.depth_max_bits == _POISON:
-            _MSD_BACKOFF[dev] = _MSD_BACKOFF_FRAMES
-        else:
-            _note_window_miss(dev)
-        _T_SEEN[dev] = fa.T
+        _frame_missed(dev, fa.depth_max_bits, fa.T)
         return forward_pipeline(cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit,
                                 sh_rest, sh_degree, pair_counts, depth_window_ok=False, need_grad=need_grad,
                                 pix_neval=pix_neval)
     if st == N.GS_NEED_CAPACITY:
-        cap = fa.T
-        tws = int(lib.gs_tile_workspace_bytes(cap, tiles, cam.cells, cam.groups))
-        tile_ws = torch.empty((tws,), dtype=torch.uint8, device=dev)
-        fb.tile_ws, fb.tile_ws_bytes, fb.capacity = tile_ws.data_ptr(), tws, cap
+        tile_ws = tile_workspace(fa.T)
         fa.resume = 1
         st = lib.gs_render_forward(C.byref(fa), s)
     N.check(st, "gs_render_forward")
     M, T = int(fa.M), int(fa.T)
     if n > 0:
-        _T_SEEN[dev] = T
-        _record_depths(dev, int(fa.depth_min_bits), int(fa.depth_max_bits))
+        _frame_done(dev, T, int(fa.depth_min_bits), int(fa.depth_max_bits))
     fr = _FastFrame()
     fr.fa, fr.frame_ws, fr.tile_ws, fr.M, fr.T = fa, frame_ws, tile_ws, M, T
     fr.groups, fr._off, fr._toff, fr.n, fr.HW, fr.tiles, fr.cells = cam.groups, None, None, n, H * W, tiles, cam.cells
     fr.slot_live_zeroed = bool(need_grad)
     fr.vis = vis
     if M == 0:
-        # renderer.py:74-83: bg once (not doubled, not clamped), zero alpha/depth
-        image = torch.tensor(cam.bg, dtype=f32, device=dev).view(3, 1, 1).repeat(1, H, W)
-        alpha = torch.zeros((1, H, W), dtype=f32, device=dev)
-        depth = torch.zeros((1, H, W), dtype=f32, device=dev)
+        image, alpha, depth = _empty_frame_outputs(cam, dev)
     return image, alpha, depth, means2d, conics, radii, vis, fr
 
 
@@ -635,18 +693,14 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
     cs = cam.to_struct()
     gst = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
 
-    means2d = torch.empty((n, 2), dtype=f32, device=dev)
-    conics = torch.empty((n, 2, 2), dtype=f32, device=dev)
-    radii = torch.empty((n,), dtype=f32, device=dev)
-    vis = torch.empty((n,), dtype=torch.bool, device=dev)
+    means2d, conics, radii, vis = _gaussian_outputs(n, dev)
     records = torch.empty((n, N.GS_RECORD_FLOATS), dtype=f32, device=dev)
     rects = torch.empty((n, 2), dtype=i32, device=dev)
     keys = torch.empty((2, n), dtype=i32, device=dev)
     vals = torch.empty((2, n), dtype=i32, device=dev)
     counters = torch.empty((N.GS_NUM_COUNTERS,), dtype=i32, device=dev)
     key_minmax = torch.empty((2 * max(1, (n + 255) // 256),), dtype=i32, device=dev)
-    window = _window_for(dev) if depth_window_ok else None
-    key_base, key_bits = window if window is not None else (0, 32)
+    window, key_base, key_bits, msd = _depth_keys(dev, depth_window_ok)
 
     StageTimer.mark("project_fwd")
     pa = N.GsProjectArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(radii), N.ptr(vis), N.ptr(records),
@@ -662,13 +716,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
         ws = torch.empty((lib.gs_radix_sort_workspace_bytes(n),), dtype=torch.uint8, device=dev)
         StageTimer.mark("depth_sort")
         alt = C.c_int32(0)
-        # (the MSD backoff counts only frames that would have taken the MSD
-        # sort; it is per process and device, not per host thread)
-        msd = _DEPTH_MSD and window is not None and 9 <= key_bits <= 31
-        backoff = _MSD_BACKOFF.get(dev, 0)
-        if msd and backoff:
-            _MSD_BACKOFF[dev] = backoff - 1
-        if msd and not backoff:
+        if msd:
             N.check(lib.gs_depth_sort_msd(N.ptr(keys[0]), N.ptr(vals[0]), N.ptr(keys[1]), N.ptr(vals[1]), n,
                                           key_bits, N.ptr(ws), ws.numel(), N.ptr(key_minmax) + 4, C.byref(alt),
                                           s), "depth sort (msd)")
@@ -682,12 +730,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
         ba = N.GsBinArgs(n, cam.tiles_x, cam.tiles_y, N.ptr(sorted_ids), N.ptr(rects), N.ptr(vis),
                          N.ptr(counters), N.ptr(key_minmax), N.ptr(bws), bws.numel(), 0, 0, N.ptr(pair_offset),
                          N.ptr(records), 0)
-        per_thread = getattr(_HOST_COUNTERS, "bufs", None)
-        if per_thread is None:
-            per_thread = _HOST_COUNTERS.bufs = {}
-        hc = per_thread.get(dev)
-        if hc is None:
-            hc = per_thread[dev] = _HostCounters()
+        hc = _host_counters(dev)
         hc.arm(ba)
         StageTimer.mark("bin_count")
         N.check(lib.gs_bin_count(C.byref(ba), s), "gs_bin_count")
@@ -695,17 +738,15 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
         # one host sync, so the GPU waits only for the read-back and launches
         num_tiles = cam.tiles_x * cam.tiles_y
         ranges = torch.empty((num_tiles, 2), dtype=i32, device=dev)
-        image = torch.empty((3, H, W), dtype=f32, device=dev)
-        alpha = torch.empty((1, H, W), dtype=f32, device=dev)
-        depth = torch.empty((1, H, W), dtype=f32, device=dev)
+        image, alpha, depth = _pixel_outputs(H, W, dev)
         pix_flags = torch.empty((H * W,), dtype=torch.uint8, device=dev)
         cell_neval = torch.empty((num_tiles, cam.cells), dtype=i32, device=dev)
         # the T-sized buffers too, at a capacity guessed from the last frame on
         # this device, and the emission queued into them before the sync (it
         # drops entries past the capacity): its kernel time hides the
         # read-back's round trip.  T above the guess: re-allocate, re-emit.
-        cap = _T_SEEN.get(dev, 0)
-        big_guess = _alloc_tile_buffers(lib, cap + cap // 4 + 4096, num_tiles, cam, dev) if cap else None
+        cap = _capacity_guess(dev)
+        big_guess = _alloc_tile_buffers(lib, cap, num_tiles, cam, dev) if cap else None
         # (M, T) reach the host through pinned memory before the emission is
         # queued, so the host wakes while the GPU still emits: gs_bin_count
         # writes them there itself (_HostCounters) -- or, where the runtime
@@ -726,13 +767,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
         StageTimer.mark("~sync")
         M, T, zmin, zmax = hc.wait(dev, ready)  # the one host sync
         if not window_holds(window, zmin, zmax):
-            # a visible depth outside the window (the sort's keys were clipped),
-            # or an MSD bucket over capacity (the depth max poisoned)
-            if zmax == _POISON:
-                _MSD_BACKOFF[dev] = _MSD_BACKOFF_FRAMES
-            else:
-                _note_window_miss(dev)
-            _T_SEEN[dev] = T
+            _frame_missed(dev, zmax, T)
             return forward_pipeline(cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit,
                                     sh_rest, sh_degree, pair_counts, depth_window_ok=False, need_grad=need_grad,
                                     pix_neval=pix_neval)
@@ -742,13 +777,8 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
     if M == 0:
         if n > 0:
-            _T_SEEN[dev] = T
-            _record_depths(dev, zmin, zmax)
-        # renderer.py:74-83: bg once (not doubled, not clamped), zero alpha/depth
-        bg = torch.tensor(cam.bg, dtype=f32, device=dev).view(3, 1, 1)
-        image = bg.repeat(1, H, W)
-        alpha = torch.zeros((1, H, W), dtype=f32, device=dev)
-        depth = torch.zeros((1, H, W), dtype=f32, device=dev)
+            _frame_done(dev, T, zmin, zmax)
+        image, alpha, depth = _empty_frame_outputs(cam, dev)
         fr.pair_offset = torch.zeros((max(n, 1),), dtype=i32, device=dev)
         return image, alpha, depth, means2d, conics, radii, vis, fr
 
@@ -781,8 +811,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
     StageTimer.mark("blend_fwd")
     N.check(lib.gs_blend_forward(C.byref(fa), s), "gs_blend_forward")
     StageTimer.mark("~end_fwd")
-    _T_SEEN[dev] = T  # (the next frame's guesses: after the launches)
-    _record_depths(dev, zmin, zmax)
+    _frame_done(dev, T, zmin, zmax)  # (the next frame's guesses: after the launches)
 
     # (the blend is queued: views for the frame cost no GPU idle time now)
     kv = L.big[:16 * L.cap].view(i32).view(4, L.cap)
@@ -825,12 +854,8 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     pair_grads = slot_live = None
     pixel_grads = g_image is not None or g_alpha is not None or g_depth is not None
     if fr.M > 0 and fr.T > 0 and pixel_grads:
-        if g_image is None:
-            g_image = torch.zeros((3, cam.image_height, cam.image_width), dtype=f32, device=dev)
-        g_image = g_image.contiguous()
-        g_alpha = None if g_alpha is None else g_alpha.contiguous()
-        g_depth = None if g_depth is None else g_depth.contiguous()
-        image, alpha, depth = _blend_outputs(outputs)
+        g_image, g_alpha, g_depth, image, alpha, depth = _pixel_cotangents(cam, g_image, g_alpha, g_depth, outputs,
+                                                                           dev)
         # one partial per (slot, cell of the batch) -- per slot at the default
         # tile, whose cells are combined on chip; only replayed entries write
         # theirs and set its flag.  Other tiles' cells run in batches of
@@ -867,23 +892,10 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
         else:
             StageTimer.mark("blend_bwd")
             N.check(lib.gs_blend_backward(C.byref(ba), s), "gs_blend_backward")
-    raw = cov3d is None
-    out = dict(out or {})
-    rows_ready = out.pop("_rows_ready", None)
-    chunks = int(out.pop("_chunks", 1)) if rows_ready is not None else 1
-
-    def buf(name, shape):
-        t = out.get(name)
-        return t.view(shape) if t is not None else torch.empty(shape, dtype=f32, device=dev)
-    d_xyz = buf("xyz", (n, 3))
-    d_cov = None if raw else torch.empty((n, 3, 3), dtype=f32, device=dev)
-    d_scl = buf("scaling", (n, 3)) if raw else None
-    d_rot = buf("rotation", (n, 4)) if raw else None
-    d_col = buf("color", (n, 3))
-    d_op = buf("opacity", (n,))
+    grads, rows_ready, chunks = _grad_buffers(out, n, cov3d is None, sh_degree, dev)
+    d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = grads
     gm = None if g_means2d is None else g_means2d.contiguous()
     gc = None if g_conics is None else g_conics.contiguous()
-    d_sh = buf("sh_rest", (n, N.GS_SH_REST, 3)) if sh_degree > 0 else None
     gst = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
     if pair_grads is not None and fr.groups < cam.groups:
         grad_sums, pair_grads, slot_live = batch_sums, None, None  # (summed batch by batch above)
@@ -896,20 +908,64 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                             N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col), N.ptr(d_op), N.ptr(d_sh),
                             N.ptr(slot_live), N.ptr(grad_sums), fr.groups)
     StageTimer.mark("project_bwd")
+    _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
+    StageTimer.mark("~end_bwd")
+    return grads
+
+
+def _pixel_cotangents(cam: CameraParams, g_image, g_alpha, g_depth, outputs, dev):
+    """The blend backward's per-pixel inputs when any pixel cotangent is
+    given: the three cotangents contiguous (a missing g_image as zeros), then
+    the forward's image, alpha, depth (_blend_outputs)."""
+    if g_image is None:
+        g_image = torch.zeros((3, cam.image_height, cam.image_width), dtype=torch.float32, device=dev)
+    g_image = g_image.contiguous()
+    g_alpha = None if g_alpha is None else g_alpha.contiguous()
+    g_depth = None if g_depth is None else g_depth.contiguous()
+    return (g_image, g_alpha, g_depth, *_blend_outputs(outputs))
+
+
+def _grad_buffers(out, n: int, raw: bool, sh_degree: int, dev):
+    """((d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh), rows_ready, chunks):
+    the projection backward's gradient tensors -- the caller's from `out`
+    (backward_pipeline), viewed to the kernels' shapes, fresh ones otherwise --
+    and out's "_rows_ready" callback with its "_chunks" (1 without a callback).
+    raw: scaling / rotation inputs (their gradients, no d_cov)."""
+    out = dict(out or {})
+    rows_ready = out.pop("_rows_ready", None)
+    chunks = int(out.pop("_chunks", 1)) if rows_ready is not None else 1
+    f32 = torch.float32
+
+    def buf(name, shape):
+        t = out.get(name)
+        return t.view(shape) if t is not None else torch.empty(shape, dtype=f32, device=dev)
+    d_xyz = buf("xyz", (n, 3))
+    d_cov = None if raw else torch.empty((n, 3, 3), dtype=f32, device=dev)
+    d_scl = buf("scaling", (n, 3)) if raw else None
+    d_rot = buf("rotation", (n, 4)) if raw else None
+    d_col = buf("color", (n, 3))
+    d_op = buf("opacity", (n,))
+    d_sh = buf("sh_rest", (n, N.GS_SH_REST, 3)) if sh_degree > 0 else None
+    return (d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh), rows_ready, chunks
+
+
+def _project_backward_ranges(lib, pb: "N.GsProjectBwdArgs", n: int, chunks: int, rows_ready, d_view, s) -> None:
+    """The projection backward of `pb`'s n Gaussians: with d_view one
+    gs_project_backward_pose over all of them (the pose gradient's reduction
+    wants one range), else gs_project_backward per row range of `chunks`,
+    rows_ready(lo, hi) called as soon as a range's rows are queued (its
+    all-reduce then overlaps the next range's kernels)."""
     if d_view is not None:
         _project_backward_pose(lib, pb, n, d_view, s)
         if rows_ready is not None:
             rows_ready(0, n)
-        StageTimer.mark("~end_bwd")
-        return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
+        return
     bounds = [n * k // chunks for k in range(chunks + 1)]
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         part = pb if (lo, hi) == (0, n) else _rows_of(pb, lo, hi)
         N.check(lib.gs_project_backward(C.byref(part), s), "gs_project_backward")
         if rows_ready is not None:
             rows_ready(lo, hi)
-    StageTimer.mark("~end_bwd")
-    return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
 
 
 def _project_backward_pose(lib, pb: "N.GsProjectBwdArgs", n: int, d_view: torch.Tensor, s) -> None:
@@ -954,13 +1010,9 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     ba.g, ba.means2d, ba.conics, ba.vis = fa.g, fa.means2d, fa.conics, fa.vis
     pair_grads = None
     if fr.M > 0 and fr.T > 0 and pixel_grads:
-        if g_image is None:
-            g_image = torch.zeros((3, cam.image_height, cam.image_width), dtype=f32, device=dev)
-        g_image = g_image.contiguous()
-        g_alpha = None if g_alpha is None else g_alpha.contiguous()
-        g_depth = None if g_depth is None else g_depth.contiguous()
+        g_image, g_alpha, g_depth, image, alpha, depth = _pixel_cotangents(cam, g_image, g_alpha, g_depth, outputs,
+                                                                           dev)
         pair_grads = torch.empty((fr.T * fr.groups, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
-        image, alpha, depth = _blend_outputs(outputs)
         ba.image, ba.alpha, ba.depth = image.data_ptr(), alpha.data_ptr(), depth.data_ptr()
         ba.g_image, ba.g_alpha, ba.g_depth = N.ptr(g_image), N.ptr(g_alpha), N.ptr(g_depth)
         ba.pair_grads = pair_grads.data_ptr()
@@ -969,21 +1021,8 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     gm = None if g_means2d is None else g_means2d.contiguous()
     gc = None if g_conics is None else g_conics.contiguous()
     ba.g_means2d, ba.g_conics = N.ptr(gm), N.ptr(gc)
-    raw = cov3d is None
-    out = dict(out or {})
-    rows_ready = out.pop("_rows_ready", None)
-    chunks = int(out.pop("_chunks", 1)) if rows_ready is not None else 1
-
-    def buf(name, shape):
-        t = out.get(name)
-        return t.view(shape) if t is not None else torch.empty(shape, dtype=f32, device=dev)
-    d_xyz = buf("xyz", (n, 3))
-    d_cov = None if raw else torch.empty((n, 3, 3), dtype=f32, device=dev)
-    d_scl = buf("scaling", (n, 3)) if raw else None
-    d_rot = buf("rotation", (n, 4)) if raw else None
-    d_col = buf("color", (n, 3))
-    d_op = buf("opacity", (n,))
-    d_sh = buf("sh_rest", (n, N.GS_SH_REST, 3)) if sh_degree > 0 else None
+    grads, rows_ready, chunks = _grad_buffers(out, n, cov3d is None, sh_degree, dev)
+    d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = grads
     ba.d_xyz, ba.d_cov3d, ba.d_scaling, ba.d_rotation = N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot)
     ba.d_color_logits, ba.d_opacity, ba.d_sh_rest = N.ptr(d_col), N.ptr(d_op), N.ptr(d_sh)
     ba.project = 1 if (chunks == 1 and d_view is None) else 0
@@ -991,29 +1030,20 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     if ev is not None:
         ba.blend_events[0], ba.blend_events[1] = ev[0].handle, ev[1].handle
     N.check(lib.gs_render_backward(C.byref(ba), s), "gs_render_backward")
-    if chunks == 1 and d_view is None:
+    if ba.project:
         if rows_ready is not None:
             rows_ready(0, n)
-        return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
-    # the projection backward per row range, each range's reduction issued
-    # as soon as its rows are queued
+        return grads
+    # the projection backward from here: per row range, each range's
+    # reduction issued as soon as its rows are queued, or with the pose gradient
     fo = fr._o()[0]
     fws = fr.frame_ws.data_ptr()
     pb = N.GsProjectBwdArgs(fa.cam, ba.g, N.ptr(means2d), N.ptr(conics), fa.vis, fws + fo[1], fws + fo[8], None,
                             None, N.ptr(gm),
                             N.ptr(gc), N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col),
                             N.ptr(d_op), N.ptr(d_sh), None, ba.grad_sums if pair_grads is not None else None, 0)
-    if d_view is not None:
-        # one range over every Gaussian, with the pose gradient's reduction
-        _project_backward_pose(lib, pb, n, d_view, s)
-        if rows_ready is not None:
-            rows_ready(0, n)
-        return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
-    bounds = [n * k // chunks for k in range(chunks + 1)]
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
-        N.check(lib.gs_project_backward(C.byref(_rows_of(pb, lo, hi)), s), "gs_project_backward")
-        rows_ready(lo, hi)
-    return d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh
+    _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
+    return grads
 
 
 def _rows_of(pb: "N.GsProjectBwdArgs", lo: int, hi: int) -> "N.GsProjectBwdArgs":

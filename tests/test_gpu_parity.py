@@ -108,16 +108,54 @@ def test_kat_front_to_back(pkg, cuda):
     assert abs(out["depth"][0, 32, 32].item() - 4 / 3) < 2e-2
 
 
-def test_all_culled_returns_bg(pkg, cuda):
-    """test_renderer.py:113-125: everything behind the camera -> image == bg, alpha 0."""
-    cam = Cam(32, 32, np.radians(60), np.radians(60))
-    st = pkg.RenderSettings(64, 64, torch.tensor([0.2, 0.3, 0.4]))
-    g = Gauss([[0, 0, -1], [0, 0, -2]], np.stack([np.diag([1e-4] * 3)] * 2), [[1, 0, 0], [0, 1, 0]], [0.5, 0.5], cuda)
-    out = pkg.GaussianRenderer().render(cam, g, st)
+_EMPTY_FRAMES: dict = {}  # (case, frame_calls) -> (out, Gaussians) of _empty_frame
+
+
+def _empty_frame(pkg, cuda, case, frame_calls):
+    """A frame that draws nothing, rendered (once per test session) through
+    the frame entry points or the stage path, and its means2D backward."""
+    key = (case, frame_calls)
+    if key not in _EMPTY_FRAMES:
+        RZ = pkg.rasterizer
+        if case == "culled":  # everything behind the camera
+            cam = Cam(32, 32, np.radians(60), np.radians(60))
+            st = pkg.RenderSettings(64, 64, torch.tensor([0.2, 0.3, 0.4]))
+            g = Gauss([[0, 0, -1], [0, 0, -2]], np.stack([np.diag([1e-4] * 3)] * 2), [[1, 0, 0], [0, 1, 0]],
+                      [0.5, 0.5], cuda)
+        else:  # an empty model
+            cam = Cam(32, 24, np.radians(60), np.radians(50))
+            st = pkg.RenderSettings(24, 32, torch.tensor([0.2, 0.3, 0.4]))
+            g = Gauss(np.zeros((0, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0), cuda)
+        saved = RZ._FRAME_CALLS
+        try:
+            RZ._FRAME_CALLS = frame_calls
+            out = pkg.GaussianRenderer().render(cam, g, st)
+            out["viewspace_points"].sum().backward()  # cotangent on means2D still flows
+        finally:
+            RZ._FRAME_CALLS = saved
+        _EMPTY_FRAMES[key] = (out, g)
+    return _EMPTY_FRAMES[key]
+
+
+def _assert_same_empty_frame(pkg, cuda, case):
+    """The frame entry points and the stage path draw the same empty frame."""
+    (a, ga), (b, gb) = (_empty_frame(pkg, cuda, case, fc) for fc in (True, False))
+    for k in ("image", "alpha", "depth", "viewspace_points", "conics", "radii", "visibility_filter"):
+        assert a[k].dtype == b[k].dtype and torch.equal(a[k], b[k]), k
+    for name in ("xyz", "cov", "feats", "op"):
+        x, y = getattr(ga, name).grad, getattr(gb, name).grad
+        assert (x is None) == (y is None) and (x is None or torch.equal(x, y)), name
+
+
+@pytest.mark.parametrize("frame_calls", [True, False])
+def test_all_culled_returns_bg(pkg, cuda, frame_calls):
+    """test_renderer.py:113-125: everything behind the camera -> image == bg, alpha 0
+    (through the frame entry points and the stage path, bit for bit alike)."""
+    out, g = _empty_frame(pkg, cuda, "culled", frame_calls)
     assert torch.allclose(out["image"].cpu(), torch.tensor([0.2, 0.3, 0.4]).view(3, 1, 1).expand(3, 64, 64))
     assert torch.count_nonzero(out["alpha"]) == 0
-    out["viewspace_points"].sum().backward()  # cotangent on means2D still flows
     assert g.xyz.grad is not None and torch.isfinite(g.xyz.grad).all()
+    _assert_same_empty_frame(pkg, cuda, "culled")
 
 
 def _oracle_scene(sc, cov, bg, wv=None):
@@ -1083,17 +1121,17 @@ def test_depth_window_miss_rerenders(pkg, cuda):
         reset()
 
 
-def test_no_gaussians(pkg, cuda):
+@pytest.mark.parametrize("frame_calls", [True, False])
+def test_no_gaussians(pkg, cuda, frame_calls):
     """N = 0 (an empty model): the early return of renderer.py:74-83 (bg once,
-    zero alpha and depth) and empty gradients."""
-    g = Gauss(np.zeros((0, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros(0), cuda)
-    out = pkg.GaussianRenderer().render(Cam(32, 24, np.radians(60), np.radians(50)), g,
-                                        pkg.RenderSettings(24, 32, torch.tensor([0.2, 0.3, 0.4])))
+    zero alpha and depth) and empty gradients (through the frame entry points
+    and the stage path, bit for bit alike)."""
+    out, g = _empty_frame(pkg, cuda, "empty", frame_calls)
     assert torch.allclose(out["image"].cpu(), torch.tensor([0.2, 0.3, 0.4]).view(3, 1, 1).expand(3, 24, 32))
     assert out["alpha"].abs().sum() == 0 and out["depth"].abs().sum() == 0
     assert out["viewspace_points"].shape == (0, 2) and out["radii"].shape == (0,)
-    out["viewspace_points"].sum().backward()
     assert g.xyz.grad is not None and g.xyz.grad.shape == (0, 3)
+    _assert_same_empty_frame(pkg, cuda, "empty")
 
 
 def test_float64_inputs_cast(pkg, cuda):

@@ -258,3 +258,168 @@ def test_fused_adam_runs_step_hooks(pkg):
     calls.clear()
     opt.step()
     assert calls == []
+
+
+@pytest.fixture
+def rz_state(pkg):
+    """rasterizer with its per-device guesses emptied for a test, restored after."""
+    RZ = pkg.rasterizer
+    dicts = (RZ._T_SEEN, RZ._DEPTH_HIST, RZ._WINDOW_STATE, RZ._MSD_BACKOFF)
+    saved, msd = [dict(d) for d in dicts], RZ._DEPTH_MSD
+    for d in dicts:
+        d.clear()
+    try:
+        yield RZ
+    finally:
+        RZ._DEPTH_MSD = msd
+        for d, s in zip(dicts, saved):
+            d.clear()
+            d.update(s)
+
+
+def _f32_bits(z):
+    import struct
+    return struct.unpack("<I", struct.pack("<f", z))[0]
+
+
+def test_capacity_guess(rz_state):
+    """The tile-entry capacity tried before T is known: nothing without a
+    frame seen, else the last T and a quarter, plus 4096."""
+    RZ, dev = rz_state, torch.device("cuda:0")
+    assert RZ._capacity_guess(dev) == 0
+    RZ._T_SEEN[dev] = 16
+    assert RZ._capacity_guess(dev) == 4116
+    assert RZ._capacity_guess(torch.device("cuda:1")) == 0
+
+
+def test_depth_keys_state_machine(rz_state):
+    """_depth_keys: 32-bit keys without a window; the MSD sort for windows of
+    9..31 bits unless switched off or backing off; the backoff is counted down
+    only by a frame that wanted the MSD sort, and never by a capture."""
+    RZ, dev = rz_state, torch.device("cuda:0")
+    assert RZ._depth_keys(dev, True) == (None, 0, 32, False)
+    RZ._DEPTH_HIST[dev] = [(_f32_bits(2.0), _f32_bits(6.0))]
+    w = RZ._window_for(dev)
+    assert w is not None and 9 <= w[1] <= 31
+    assert RZ._depth_keys(dev, True) == (w, w[0], w[1], True)
+    assert RZ._depth_keys(dev, False) == (None, 0, 32, False)
+    assert RZ._depth_keys(dev, True, window=(5, 12)) == ((5, 12), 5, 12, True)  # (GraphedStep.window)
+    assert RZ._depth_keys(dev, True, window=None) == (None, 0, 32, False)
+    assert dev not in RZ._MSD_BACKOFF
+    RZ._MSD_BACKOFF[dev] = 2
+    assert RZ._depth_keys(dev, True, consume=False) == (w, w[0], w[1], False)
+    assert RZ._MSD_BACKOFF[dev] == 2
+    assert RZ._depth_keys(dev, True) == (w, w[0], w[1], False)
+    assert RZ._MSD_BACKOFF[dev] == 1
+    assert RZ._depth_keys(dev, False)[3] is False and RZ._MSD_BACKOFF[dev] == 1  # (no window: not an MSD frame)
+    assert RZ._depth_keys(dev, True)[3] is False and RZ._MSD_BACKOFF[dev] == 0
+    assert RZ._depth_keys(dev, True)[3] is True  # (the backoff is spent)
+    RZ._MSD_BACKOFF[dev] = 2
+    RZ._DEPTH_MSD = False
+    assert RZ._depth_keys(dev, True) == (w, w[0], w[1], False) and RZ._MSD_BACKOFF[dev] == 2
+    RZ._DEPTH_MSD = True
+    RZ._DEPTH_HIST[dev] = [(_f32_bits(3.0), _f32_bits(3.0))]  # a single depth: a window of a few bits
+    w = RZ._window_for(dev)
+    assert w is not None and w[1] <= 8
+    assert RZ._depth_keys(dev, True) == (w, w[0], w[1], False) and RZ._MSD_BACKOFF[dev] == 2
+
+
+def test_frame_missed_and_done(rz_state):
+    """A frame to render again: a poisoned depth max starts the MSD backoff
+    and is no window miss, anything else is one; both keep the frame's T.  A
+    finished frame leaves its T and its depth range."""
+    RZ, dev = rz_state, torch.device("cuda:0")
+    misses = lambda: RZ.depth_window_stats(dev)["misses"]
+    RZ._frame_missed(dev, 0xFFFFFFFF, 700)
+    assert RZ._MSD_BACKOFF[dev] == RZ._MSD_BACKOFF_FRAMES and misses() == 0 and RZ._T_SEEN[dev] == 700
+    RZ._MSD_BACKOFF.clear()
+    RZ._frame_missed(dev, _f32_bits(9.0), 900)
+    assert misses() == 1 and dev not in RZ._MSD_BACKOFF and RZ._T_SEEN[dev] == 900
+    RZ._frame_missed(dev, 0, 5)
+    assert misses() == 2 and RZ._T_SEEN[dev] == 5
+    frames = RZ.depth_window_stats(dev)["frame"]
+    RZ._frame_done(dev, 1234, _f32_bits(2.0), _f32_bits(6.0))
+    assert RZ._T_SEEN[dev] == 1234 and RZ._DEPTH_HIST[dev] == [(_f32_bits(2.0), _f32_bits(6.0))]
+    assert RZ.depth_window_stats(dev)["frame"] == frames + 1
+    RZ._frame_done(dev, 0, 0xFFFFFFFF, 0)  # nothing visible: counted, no range
+    assert RZ._T_SEEN[dev] == 0 and len(RZ._DEPTH_HIST[dev]) == 1
+    assert RZ.depth_window_stats(dev)["frame"] == frames + 2
+
+
+def test_host_counter_sequence(pkg):
+    """The counters' sequence word: 1 .. 2^31 - 1, wrapping past the cleared 0."""
+    hc = object.__new__(pkg.rasterizer._HostCounters)  # (no pinned buffer here)
+    hc.seq = 0
+    assert [hc.next_seq(), hc.next_seq()] == [1, 2] and hc.seq == 2
+    hc.seq = 0x7FFFFFFE
+    assert [hc.next_seq(), hc.next_seq()] == [0x7FFFFFFF, 1]
+
+
+def test_grad_buffers(pkg):
+    """_grad_buffers: the caller's tensors from `out` are the kernels'
+    destinations (viewed to the kernels' shapes), the rest is allocated; the
+    row-range callback and its chunk count are taken out of `out`."""
+    RZ, n, cpu = pkg.rasterizer, 6, torch.device("cpu")
+    ready = lambda lo, hi: None
+    out = {"xyz": torch.zeros(n * 3), "opacity": torch.zeros(n, 1), "color": torch.zeros(n, 1, 3),
+           "_rows_ready": ready, "_chunks": 3}
+    (d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh), rows_ready, chunks = RZ._grad_buffers(out, n, True, 0, cpu)
+    assert rows_ready is ready and chunks == 3
+    assert "_rows_ready" in out and "_chunks" in out  # (the caller's dict is left alone)
+    assert d_xyz.data_ptr() == out["xyz"].data_ptr() and d_xyz.shape == (n, 3)
+    assert d_op.data_ptr() == out["opacity"].data_ptr() and d_op.shape == (n,)
+    assert d_col.data_ptr() == out["color"].data_ptr() and d_col.shape == (n, 3)
+    assert d_cov is None and d_sh is None
+    assert d_scl.shape == (n, 3) and d_rot.shape == (n, 4) and d_scl.dtype == torch.float32
+    grads, rows_ready, chunks = RZ._grad_buffers({"_chunks": 4}, n, False, 2, cpu)
+    assert rows_ready is None and chunks == 1  # (no callback: one range)
+    assert grads[1].shape == (n, 3, 3) and grads[2] is None and grads[3] is None
+    assert grads[6].shape == (n, pkg._native.GS_SH_REST, 3)
+    grads, rows_ready, chunks = RZ._grad_buffers(None, n, True, 0, cpu)
+    assert rows_ready is None and chunks == 1 and grads[0].shape == (n, 3)
+    assert RZ._grad_buffers({"_rows_ready": ready}, n, True, 0, cpu)[1:] == (ready, 1)
+
+
+class _FakeLib:
+    """Records the projection backward's calls: (entry point, the struct passed, its g.n)."""
+
+    def __init__(self):
+        self.calls = []
+
+    def gs_project_backward(self, ref, stream):
+        self.calls.append(("gs_project_backward", ref._obj, ref._obj.g.n))
+        return 0
+
+    def gs_project_backward_pose(self, ref, stream):
+        self.calls.append(("gs_project_backward_pose", ref._obj, ref._obj.bwd.g.n))
+        return 0
+
+
+def test_project_backward_ranges(pkg):
+    """_project_backward_ranges: n * k // chunks row bounds, one launch per
+    range and its rows_ready right after; the struct itself for the whole
+    range; with d_view one pose launch over every Gaussian."""
+    RZ, N = pkg.rasterizer, pkg._native
+    n = 10
+    pb = N.GsProjectBwdArgs()
+    pb.g.n = n
+    lib, log = _FakeLib(), []
+
+    def ready(lo, hi):
+        log.append((lo, hi, len(lib.calls)))
+    RZ._project_backward_ranges(lib, pb, n, 3, ready, None, None)
+    assert [c[0] for c in lib.calls] == ["gs_project_backward"] * 3
+    assert [c[2] for c in lib.calls] == [3, 3, 4] and all(c[1] is not pb for c in lib.calls)
+    assert log == [(0, 3, 1), (3, 6, 2), (6, 10, 3)]  # (each range announced once it is queued)
+    assert pb.g.n == n
+    lib.calls.clear(), log.clear()
+    RZ._project_backward_ranges(lib, pb, n, 1, ready, None, None)
+    assert len(lib.calls) == 1 and lib.calls[0][1] is pb and log == [(0, 10, 1)]
+    lib.calls.clear(), log.clear()
+    RZ._project_backward_ranges(lib, pb, n, 1, None, None, None)
+    assert len(lib.calls) == 1 and lib.calls[0][1] is pb
+    lib.calls.clear()
+    d_view = torch.zeros(12)
+    RZ._project_backward_ranges(lib, pb, n, 3, ready, d_view, None)  # (the pose reduction wants one range)
+    assert [(c[0], c[2]) for c in lib.calls] == [("gs_project_backward_pose", n)] and log == [(0, 10, 1)]
+    assert lib.calls[0][1].d_view == d_view.data_ptr()
