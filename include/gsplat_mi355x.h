@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GS_ABI_VERSION 22
+#define GS_ABI_VERSION 23
 #define GS_DEFAULT_TILE 16    /* renderer.py:24 tile_size default */
 #define GS_MAX_TILE 16384     /* tile_size in [1, GS_MAX_TILE]; the reference accepts any int, and a tile
                                  of at least max(W, H) renders the same as any larger one (one tile
@@ -457,6 +457,11 @@ typedef struct gs_adam_tensor {
 typedef struct gs_adam_args {
   int32_t num_tensors;
   float beta1, beta2, eps;
+  /* The gradient's weights 1 - beta1 and 1 - beta2, formed in double by the
+   * caller and rounded once: 1.f - (float)0.999 is 1.3e-5 below 0.001, which
+   * the second moment would carry while the bias corrections (formed in
+   * double) assume 0.001.  0: 1.f - beta in fp32. */
+  float one_minus_beta1, one_minus_beta2;
   gs_adam_tensor t[GS_ADAM_MAX_TENSORS];
   /* Replayed steps (a captured graph whose kernel arguments are fixed):
    * skip_flag: optional device word -- non-zero: the launch updates nothing
@@ -528,7 +533,9 @@ gs_status gs_loss_backward(const gs_loss_args *a, gs_stream_t stream);
  * Output order: kept originals, split "-" children, split "+" children,
  * clones; each in the original index order.  (The reference cannot run
  * these: _append_points reads a missing `_scaling_log` (:229).)  Two
- * phases: gs_densify_count writes counters, the caller sizes the outputs. */
+ * phases: gs_densify_count writes counters, the caller sizes the outputs
+ * (n_out = 0, everything pruned: there is nothing to emit, and
+ * gs_densify_emit refuses the NULL outputs an empty allocation has). */
 #define GS_DENSIFY_SPLIT 1
 #define GS_DENSIFY_CLONE 2
 #define GS_DENSIFY_PRUNE 4

@@ -27,7 +27,7 @@ GS_RECORD_FLOATS = 12
 GS_PAIR_GRAD_FLOATS = 10
 GS_PARTIAL_STRIDE = 10  # floats between partials in pair_grads (dense; gs_partial_groups per entry)
 GS_NUM_COUNTERS = 8  # M, T, depth-bits min / max, frame status, T_eff (GS_NUM_COUNTERS in the header)
-GS_ABI_VERSION = 22
+GS_ABI_VERSION = 23
 # frame status bits (counters[4]; the pinned counters' [5]): what a device-resident
 # frame could not do on the device, so its step is redone on the host path
 GS_FRAME_NEED_CAPACITY, GS_FRAME_WINDOW_MISS, GS_FRAME_EMPTY = 1, 2, 4
@@ -164,6 +164,7 @@ class GsAdamTensor(C.Structure):
 class GsAdamArgs(C.Structure):
     _fields_ = [
         ("num_tensors", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+        ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float),
         ("t", GsAdamTensor * GS_ADAM_MAX_TENSORS), ("skip_flag", _vp), ("hyper", _vp), ("hyper_row", _vp),
     ]
 

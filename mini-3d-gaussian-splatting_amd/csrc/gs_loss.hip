@@ -206,7 +206,10 @@ __global__ __launch_bounds__(kThreads) void k_loss_fwd(gs_loss_args a, Window wi
     const float A1 = 2.f * mx * my + a.c1, A2 = 2.f * sxy + a.c2;
     const float B1 = mx * mx + my * my + a.c1, B2 = sxx + syy + a.c2;
     const float D = B1 * B2, S = (A1 * A2) / D;
-    ss += fminf(fmaxf(S, 0.f), 1.f);  // loss.py:39 (NaN -> 0 here; torch would keep NaN)
+    // loss.py:39 (NaN -> 0 here; torch would keep NaN).  The sum is of 1 - SSIM:
+    // a sum of SSIM carries its rounding (~1e-8 of the mean) into 1 - mean,
+    // whatever is left of D-SSIM as the images converge
+    ss += 1.f - fminf(fmaxf(S, 0.f), 1.f);
     if (a.maps) {
       // d clamp(S)/dS: 1 on [0,1] (torch clamp_backward, boundary-inclusive), else 0
       const float g = (S >= 0.f && S <= 1.f) ? 1.f : 0.f;
@@ -241,7 +244,7 @@ __global__ __launch_bounds__(1024) void k_loss_final(gs_loss_args a, const float
   }
   if (threadIdx.x == 0) {
     const double n = (double)a.channels * a.height * a.width;
-    const float l1 = (float)(s_b[0] / n), dssim = (float)(1.0 - s_a[0] / n);
+    const float l1 = (float)(s_b[0] / n), dssim = (float)(s_a[0] / n);
     a.out[0] = (1.f - a.lambda_dssim) * l1 + a.lambda_dssim * dssim;  // loss.py:58
     a.out[1] = l1;
     a.out[2] = dssim;

@@ -2070,6 +2070,7 @@ struct FusedAdamArgs {
   float *param_out[5], *exp_avg[5], *exp_avg_sq[5];
   float lr[5], bc1[5], bc2s[5];
   float beta1, beta2, eps;
+  float om1, om2;            // 1 - beta1, 1 - beta2 (gs_adam_args.one_minus_beta*)
   const uint32_t *skip_flag;
   const float *hyper;        // [row][GS_ADAM_MAX_TENSORS][3] (gs_adam_args.hyper) or NULL
   const uint32_t *hyper_row;
@@ -2096,7 +2097,7 @@ struct AdamOut {
         m[kAdamOff[t] + k] = f.exp_avg[t][i];
         v[kAdamOff[t] + k] = f.exp_avg_sq[t][i];
       }
-    const float om1 = 1.f - f.beta1, om2 = 1.f - f.beta2;
+    const float om1 = f.om1, om2 = f.om2;
 #pragma unroll
     for (int t = 0; t < 5; ++t) {
       float lr = f.lr[t], bc1 = f.bc1[t], b2s = f.bc2s[t];
@@ -2522,7 +2523,7 @@ __global__ __launch_bounds__(kBlock) void k_adam(gs_adam_args a, int4 firsts0, i
   }
   float *const pout = t.param_out ? t.param_out : t.param;  // (in place unless an output is given)
   const int64_t base = (int64_t)(blockIdx.x - starts[ti]) * kAdamChunk;
-  const float b1 = a.beta1, b2 = a.beta2, om1 = 1.f - b1, om2 = 1.f - b2;
+  const float b2 = a.beta2, om1 = a.one_minus_beta1, om2 = a.one_minus_beta2;
   const float step = lr / bc1;
   const bool vec = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
                      reinterpret_cast<uintptr_t>(t.exp_avg) | reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
@@ -3022,6 +3023,8 @@ gs_status gs_project_backward_adam(const gs_project_bwd_args *a, const gs_adam_a
     return fail(GS_ERR_INVALID_ARG, "%s: dense parameter rows", what);
   f.beta1 = adam->beta1;
   f.beta2 = adam->beta2;
+  f.om1 = adam->one_minus_beta1 != 0.f ? adam->one_minus_beta1 : 1.f - adam->beta1;
+  f.om2 = adam->one_minus_beta2 != 0.f ? adam->one_minus_beta2 : 1.f - adam->beta2;
   f.eps = adam->eps;
   f.skip_flag = adam->skip_flag;
   f.hyper = adam->hyper;
@@ -3053,6 +3056,8 @@ gs_status gs_adam_step(const gs_adam_args *a, gs_stream_t stream) {
   if (nblk > 0x7fffffffLL) return fail(GS_ERR_UNSUPPORTED, "%s: too many elements", "gs_adam_step");
   // tensors without grad get no blocks: zero-length ranges in the table
   gs_adam_args c = *a;
+  if (c.one_minus_beta1 == 0.f) c.one_minus_beta1 = 1.f - c.beta1;
+  if (c.one_minus_beta2 == 0.f) c.one_minus_beta2 = 1.f - c.beta2;
   for (int i = a->num_tensors; i < GS_ADAM_MAX_TENSORS; ++i) c.t[i].grad = nullptr;
   k_adam<<<(unsigned)nblk, kBlock, 0, (hipStream_t)stream>>>(
       c, make_int4(starts[0], starts[1], starts[2], starts[3]), make_int4(starts[4], starts[5], starts[6], starts[7]));

@@ -233,7 +233,8 @@ class GaussianModel(nn.Module):
         m_out = [torch.empty_like(o) if "exp_avg" in st else None for o, st in zip(outs, states)]
         v_out = [torch.empty_like(o) if "exp_avg_sq" in st else None for o, st in zip(outs, states)]
         a.out, a.adam_m_out, a.adam_v_out = arrays(outs), arrays(m_out), arrays(v_out)
-        N.check(lib.gs_densify_emit(C.byref(a), stream), "gs_densify_emit")
+        if n_out:  # (every Gaussian pruned: the empty outputs have no address to emit to)
+            N.check(lib.gs_densify_emit(C.byref(a), stream), "gs_densify_emit")
         new = [nn.Parameter(o) for o in outs]
         if optimizer is not None:
             remap = {id(p): (q, st, m, v) for p, q, st, m, v in zip(params, new, states, m_out, v_out)}

@@ -245,6 +245,7 @@ class GraphedStep:
             aa = N.GsAdamArgs()
             aa.num_tensors = len(self.plan)
             aa.beta1, aa.beta2, aa.eps = self.adam_key
+            aa.one_minus_beta1, aa.one_minus_beta2 = 1.0 - self.adam_key[0], 1.0 - self.adam_key[1]
             for k, (p, g, _) in enumerate(self.plan):
                 st = self.optimizer.state[p]
                 out = self.optimizer.param_out.get(p)

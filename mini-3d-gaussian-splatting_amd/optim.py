@@ -72,6 +72,7 @@ class FusedAdam(torch.optim.Optimizer):
                 chunk = ds[i:i + N.GS_ADAM_MAX_TENSORS]
                 a = N.GsAdamArgs()
                 a.num_tensors, a.beta1, a.beta2, a.eps = len(chunk), b1, b2, eps
+                a.one_minus_beta1, a.one_minus_beta2 = 1.0 - b1, 1.0 - b2  # (in double, rounded once)
                 for k, (p, m, v, g, rows, lr, bc1, bc2s, out) in enumerate(chunk):
                     if lo is None:
                         off, num = 0, p.numel()
@@ -177,6 +178,7 @@ class FusedAdam(torch.optim.Optimizer):
                     chunk = idx[j:j + N.GS_ADAM_MAX_TENSORS]
                     a = N.GsAdamArgs()
                     a.num_tensors, a.beta1, a.beta2, a.eps = len(chunk), b1, b2, eps
+                    a.one_minus_beta1, a.one_minus_beta2 = 1.0 - b1, 1.0 - b2  # (in double, rounded once)
                     for k, i in enumerate(chunk):
                         pp, m, v, o, num = plan[i][:5]
                         a.t[k] = N.GsAdamTensor(pp, m, v, None, num, 0.0, 1.0, 1.0, o or None)

@@ -87,7 +87,7 @@ def test_exports(pkg):
         assert name in pkg.__all__ and hasattr(pkg, name)
     assert "gs_project_backward_pose" in pkg._native.EXPORTS
     assert hasattr(pkg._native.load(), "gs_project_backward_pose")
-    assert pkg._native.GS_ABI_VERSION == 22 == pkg._native.load().gs_abi_version()
+    assert pkg._native.GS_ABI_VERSION == 23 == pkg._native.load().gs_abi_version()
 
 
 def test_pose_struct_layout_matches_c(pkg, tmp_path):
