@@ -1,6 +1,6 @@
 """Builds libgsplat_mi355x.so in-tree with hipcc for gfx950.
 
-    python mini-3d-gaussian-splatting_amd/build.py [--force]
+    python mini-3d-gaussian-splatting_amd/build.py [--force | --print-sources]
 
 The built .so is git-ignored but travels to the GPU box with the repo
 snapshot (it is not in .gpurunignore).
@@ -13,8 +13,13 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", n) for n in ("gsplat_mi355x.hip", "gs_loss.hip", "gs_densify.hip", "gs_render.hip")]
-HDR = [os.path.join(ROOT, "include", "gsplat_mi355x.h"), os.path.join(HERE, "csrc", "gs_internal.h")]
+# The one list of the library's sources (tools/*.sh take it from --print-sources;
+# tests/test_abi.py checks it against the csrc/ and include/ directories).
+SRC = [os.path.join(HERE, "csrc", n) for n in (
+    "gs_common.hip", "gs_project.hip", "gs_sort.hip", "gs_bin.hip", "gs_blend.hip", "gs_adam.hip",
+    "gs_loss.hip", "gs_densify.hip", "gs_render.hip")]
+HDR = [os.path.join(ROOT, "include", "gsplat_mi355x.h"), os.path.join(HERE, "csrc", "gs_internal.h"),
+       os.path.join(HERE, "csrc", "gs_device.h")]
 OUT = os.path.join(HERE, "libgsplat_mi355x.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -57,4 +62,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
+    if "--print-sources" in sys.argv:  # one path per line, nothing else
+        print("\n".join(SRC))
+    else:
+        build(force="--force" in sys.argv)

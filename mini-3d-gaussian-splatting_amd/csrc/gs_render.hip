@@ -1,7 +1,8 @@
 // gs_render.hip -- one-call frame orchestration (include/gsplat_mi355x.h,
 // "Frame entry points"): gs_render_forward / gs_render_backward run the
-// stage entry points of gsplat_mi355x.hip in the order GaussianRenderer.render
-// (renderer.py:31-114) and its autograd backward need, inside the library,
+// stage entry points (gs_project.hip, gs_sort.hip, gs_bin.hip, gs_blend.hip)
+// in the order GaussianRenderer.render (renderer.py:31-114) and its autograd
+// backward need, inside the library,
 // over two caller-owned workspaces laid out here.  A frame then costs the
 // host one call per direction (plus the projection backward's), where the
 // Python host issued ~15 library calls and ~20 allocations per frame: the

@@ -113,3 +113,20 @@ def test_workspace_queries(pkg):
     # partials per entry of a one-batch backward: one per cell at every tile size (large
     # tiles may replay their cells in batches, rasterizer.cell_batch); 0 out of range
     assert [lib.gs_partial_groups(t) for t in (1, 16, 256, 257, 4096, 0, 16385)] == [1, 4, 1024, 1089, 262144, 0, 0]
+
+
+def test_build_lists_name_every_source_and_header():
+    """build.SRC / build.HDR are the library's only file list (the tools take
+    it from build.py --print-sources): every .hip under csrc/ is compiled, and
+    every header under csrc/ and include/ feeds source_hash() and stale()."""
+    import glob
+    import sys
+    import __graft_entry__ as ge
+    build = ge._load_build_module()
+    csrc = os.path.join(ge.PKG_DIR, "csrc")
+    assert sorted(build.SRC) == sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert sorted(build.HDR) == sorted(glob.glob(os.path.join(csrc, "*.h")) +
+                                       glob.glob(os.path.join(ROOT, "include", "*.h")))
+    out = subprocess.run([sys.executable, os.path.join(ge.PKG_DIR, "build.py"), "--print-sources"],
+                         capture_output=True, text=True, check=True).stdout
+    assert out.splitlines() == build.SRC

@@ -1,4 +1,4 @@
-"""The blend's exp (csrc/gsplat_mi355x.hip exp_blend), restated in numpy fp32
+"""The blend's exp (csrc/gs_blend.hip exp_blend), restated in numpy fp32
 with an ideal 2^x for v_exp_f32: its 5-operation form on t = -s/2 gives the
 same values as the 6-operation form it replaced in round 6 (the remainder in
 log2 units on s), and both are within 1 ulp of exp over the range the blend

@@ -1,5 +1,5 @@
 """A lane-level model of k_tile_ranges' empty-tile fill (wave_fill_runs in
-gsplat_mi355x.hip), run on the CPU: 64-lane waves, the last wave partial
+gs_bin.hip), run on the CPU: 64-lane waves, the last wave partial
 (lanes past num_pairs leave the kernel first), gaps longer than 32 tiles
 written by the wave's active lanes together.  Every tile's range must be
 written and equal to the bisection of the sorted keys (empty tiles: start ==

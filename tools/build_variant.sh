@@ -5,8 +5,8 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 name=$1; shift
 mkdir -p "$R/ab"
-C=$R/mini-3d-gaussian-splatting_amd/csrc
+mapfile -t SRC < <(python "$R/mini-3d-gaussian-splatting_amd/build.py" --print-sources)  # (the one source list)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
-  -Wall -Wno-unused-function -I "$R/include" "$@" "$C/gsplat_mi355x.hip" "$C/gs_loss.hip" "$C/gs_densify.hip" "$C/gs_render.hip" \
+  -Wall -Wno-unused-function -I "$R/include" "$@" "${SRC[@]}" \
   -o "$R/ab/$name.so"
 echo "built ab/$name.so"

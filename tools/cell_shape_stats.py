@@ -1,7 +1,7 @@
 """Cell-shape study (not product code): how many (entry, cell) visits the
 blend makes at C3 with 8x8 cells versus 8x16 "tall" cells (two pixels per
 lane), from the projected means / conics / radii of one render and the
-cell_hit box test of gsplat_mi355x.hip.  usage: python tools/cell_shape_stats.py"""
+cell_hit box test of gs_blend.hip.  usage: python tools/cell_shape_stats.py"""
 import importlib
 import math
 import sys

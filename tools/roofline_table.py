@@ -15,7 +15,7 @@ import re
 import sys
 
 PEAK = 8000.0  # GB/s (HBM3E spec)
-SORT_CHUNK = 2048  # radix sort block (gsplat_mi355x.hip kSortChunk)
+SORT_CHUNK = 2048  # radix sort block (gs_sort.hip kSortChunk)
 ALIAS = {"k_tile_ranges4": "k_tile_ranges"}  # (four positions per thread at the default tile: the same model)
 
 

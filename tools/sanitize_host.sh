@@ -22,10 +22,11 @@ import pytest
 sys.exit(pytest.main(["-q", "$R/tests/test_oracle.py", "-p", "no:cacheprovider"]))
 PY
 RT=/opt/rocm/lib/llvm/lib/clang/22/lib/linux
-C=$R/mini-3d-gaussian-splatting_amd/csrc
+mapfile -t SRC < <(python "$R/mini-3d-gaussian-splatting_amd/build.py" --print-sources)  # (the one source list)
+[ ${#SRC[@]} -gt 0 ] || exit 1
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -shared -ffp-contract=off -fno-slp-vectorize \
   -Xarch_host -fsanitize=undefined -Xarch_host -shared-libsan -Wl,-rpath,$RT -I "$R/include" \
-  "$C/gsplat_mi355x.hip" "$C/gs_loss.hip" "$C/gs_densify.hip" -o "$T/libgs_ubsan.so" || exit 1
+  "${SRC[@]}" -o "$T/libgs_ubsan.so" || exit 1
 export UBSAN_OPTIONS=print_stacktrace=1
 python "$T/run_oracle.py" > "$T/oracle.log" 2>&1; r1=$?
 (cd "$R" && GS_LIB_PATH="$T/libgs_ubsan.so" python -m pytest tests/test_abi.py tests/test_host.py -q -p no:cacheprovider) \
