@@ -382,7 +382,7 @@ gs_status gs_blend_backward_lane_stats(const gs_blend_bwd_args *a, uint64_t *his
 typedef struct gs_project_bwd_args {
   gs_camera cam;
   gs_gaussians g;
-  const float *means2d, *conics;
+  const float *means2d, *conics; /* the forward's (required; the raw path forms its own conic, in double) */
   const uint8_t *vis;
   const uint32_t *rects;
   const uint32_t *pair_offset;

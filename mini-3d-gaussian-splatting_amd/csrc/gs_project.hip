@@ -615,20 +615,49 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
   }
   // The screen-space part (conic inverse backward, dL/dJ, dL/dmean) runs in
   // double: for needle Gaussians Q = inv(cov2d) has condition numbers ~1e6
-  // and dV = -Q G Q cancels against J C in dL/dJ.  The 3D part (J^T dV J,
-  // Rv^T dC Rv, scale/rotation) is plain fp32 with the triple products
-  // factored -- f64 exp/div/sqrt and 81-term sums made this kernel 3x slower.
+  // and dV = -Q G Q cancels against J C in dL/dJ.  The cov3d path's 3D part
+  // (J^T dV J, Rv^T dC Rv) is plain fp32 with the triple products factored.
+  // The raw path's is double too, but short: the 2x3 P = J Rv Rq takes dV to the
+  // Gaussian's own frame without forming dC or dS (an earlier all-double
+  // version, with f64 exp and 81-term sums, made this kernel 3x slower; this
+  // one measured 1.104 against 1.117 ms per C3 step for the fp32 3D part).
   const gs_camera &c = a.cam;
   const float *R = c.view;  // rows [R | t]
   auto dot3 = [](float a0, float a1, float a2, float b0, float b1, float b2) {
     return __builtin_fmaf(a0, b0, __builtin_fmaf(a1, b1, a2 * b2));
   };
-  float Sf[9];
+  // Raw path: the rotation R(q / |q|), Sigma = R diag(s^2) R^T and (below) the
+  // conic in double.  A rotation rounded to fp32 turns a needle's axes by
+  // ~1e-7 rad, which moves a nearly cancelling rotation gradient by 1e-2 of
+  // itself (tests/test_project_stage.py); s = expf(scaling) stays fp32, a
+  // relative perturbation of one scale that nothing amplifies.
+  double Sf[9], Rqd[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, s2d[3] = {0.0, 0.0, 0.0}, qd[4] = {0.0, 0.0, 0.0, 0.0};
+  double iqd = 0.0;
+  const float *sc = kHot ? scl_pre : a.g.scaling + (int64_t)g * 3, *rq = kHot ? rot_pre : a.g.rotation + (int64_t)g * 4;
   if (!raw) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) Sf[k] = a.g.cov3d[9 * (size_t)g + k];
   } else {
-    cov_from_raw(kHot ? scl_pre : a.g.scaling + (int64_t)g * 3, kHot ? rot_pre : a.g.rotation + (int64_t)g * 4, Sf);
+    const double qw = rq[0], qx = rq[1], qy = rq[2], qz = rq[3];
+    double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+    qn = qn < 1e-12 ? 1e-12 : qn;
+    iqd = 1.0 / qn;
+    const double w = qw * iqd, x = qx * iqd, y = qy * iqd, z = qz * iqd;
+    qd[0] = w; qd[1] = x; qd[2] = y; qd[3] = z;
+    Rqd[0] = 1.0 - 2.0 * (y * y + z * z); Rqd[1] = 2.0 * (x * y - w * z); Rqd[2] = 2.0 * (x * z + w * y);
+    Rqd[3] = 2.0 * (x * y + w * z); Rqd[4] = 1.0 - 2.0 * (x * x + z * z); Rqd[5] = 2.0 * (y * z - w * x);
+    Rqd[6] = 2.0 * (x * z - w * y); Rqd[7] = 2.0 * (y * z + w * x); Rqd[8] = 1.0 - 2.0 * (x * x + y * y);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double s = (double)expf(sc[k]);
+      s2d[k] = s * s;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        Sf[i * 3 + j] = Rqd[i * 3] * s2d[0] * Rqd[j * 3] + Rqd[i * 3 + 1] * s2d[1] * Rqd[j * 3 + 1] +
+                        Rqd[i * 3 + 2] * s2d[2] * Rqd[j * 3 + 2];
   }
   double Xc[3];
 #pragma unroll
@@ -649,12 +678,6 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
       C[i * 3 + j] = RS[i * 3] * R[j * 4] + RS[i * 3 + 1] * R[j * 4 + 1] + RS[i * 3 + 2] * R[j * 4 + 2];
   const double iz = 1.0 / Z, iz2 = iz * iz, iz3 = iz2 * iz;
   const double Jd[6] = {fx * iz, 0.0, -fx * X * iz2, 0.0, -fy * iz, fy * Y * iz2};
-  const double Q[4] = {Qf.x, Qf.y, Qf.z, Qf.w};
-  // d cov2d = -Q^T G Q^T (inverse backward)
-  const double QG0 = Q[0] * G[0] + Q[2] * G[2], QG1 = Q[0] * G[1] + Q[2] * G[3];
-  const double QG2 = Q[1] * G[0] + Q[3] * G[2], QG3 = Q[1] * G[1] + Q[3] * G[3];
-  const double dVd[4] = {-(QG0 * Q[0] + QG1 * Q[1]), -(QG0 * Q[2] + QG1 * Q[3]), -(QG2 * Q[0] + QG3 * Q[1]),
-                         -(QG2 * Q[2] + QG3 * Q[3])};
   double JCt[6], JCn[6];  // J C^T, J C
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -663,6 +686,24 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
       JCt[i * 3 + j] = Jd[i * 3] * C[j * 3] + Jd[i * 3 + 1] * C[j * 3 + 1] + Jd[i * 3 + 2] * C[j * 3 + 2];
       JCn[i * 3 + j] = Jd[i * 3] * C[j] + Jd[i * 3 + 1] * C[3 + j] + Jd[i * 3 + 2] * C[6 + j];
     }
+  double Q[4] = {Qf.x, Qf.y, Qf.z, Qf.w};
+  if (raw) {  // the conic of the double Sigma (the forward's is inv of an fp32 cov2d: off by eps cond(cov2d))
+    double V[4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        V[i * 2 + j] = JCn[i * 3] * Jd[j * 3] + JCn[i * 3 + 1] * Jd[j * 3 + 1] + JCn[i * 3 + 2] * Jd[j * 3 + 2];
+    V[0] += 1e-6;
+    V[3] += 1e-6;
+    const double idet = 1.0 / (V[0] * V[3] - V[1] * V[2]);
+    Q[0] = V[3] * idet; Q[1] = -V[1] * idet; Q[2] = -V[2] * idet; Q[3] = V[0] * idet;
+  }
+  // d cov2d = -Q^T G Q^T (inverse backward)
+  const double QG0 = Q[0] * G[0] + Q[2] * G[2], QG1 = Q[0] * G[1] + Q[2] * G[3];
+  const double QG2 = Q[1] * G[0] + Q[3] * G[2], QG3 = Q[1] * G[1] + Q[3] * G[3];
+  const double dVd[4] = {-(QG0 * Q[0] + QG1 * Q[1]), -(QG0 * Q[2] + QG1 * Q[3]), -(QG2 * Q[0] + QG3 * Q[1]),
+                         -(QG2 * Q[2] + QG3 * Q[3])};
   double dJ[6];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -705,70 +746,71 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
                            (dCd[i] * RS[j] + dCd[3 + i] * RS[3 + j] + dCd[6 + i] * RS[6 + j]);
     }
   }
-  float J[6], dV[4];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) J[k] = (float)Jd[k];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) dV[k] = (float)dVd[k];
-  float dVJ[6], dC[9];  // dC = J^T dV J
-#pragma unroll
-  for (int k = 0; k < 2; ++k)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) dVJ[k * 3 + j] = __builtin_fmaf(dV[k * 2], J[j], dV[k * 2 + 1] * J[3 + j]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) dC[i * 3 + j] = __builtin_fmaf(J[i], dVJ[j], J[3 + i] * dVJ[3 + j]);
-  float dCR[9], dS[9];  // dS = Rv^T dC Rv
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) dCR[k * 3 + j] = dot3(dC[k * 3], dC[k * 3 + 1], dC[k * 3 + 2], R[j], R[4 + j], R[8 + j]);
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) dS[i * 3 + j] = dot3(R[i], R[4 + i], R[8 + i], dCR[j], dCR[3 + j], dCR[6 + j]);
   if (!raw) {
+    float J[6], dV[4];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) J[k] = (float)Jd[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dV[k] = (float)dVd[k];
+    float dVJ[6], dC[9];  // dC = J^T dV J
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dVJ[k * 3 + j] = __builtin_fmaf(dV[k * 2], J[j], dV[k * 2 + 1] * J[3 + j]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dC[i * 3 + j] = __builtin_fmaf(J[i], dVJ[j], J[3 + i] * dVJ[3 + j]);
+    float dCR[9], dS[9];  // dS = Rv^T dC Rv
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dCR[k * 3 + j] = dot3(dC[k * 3], dC[k * 3 + 1], dC[k * 3 + 2], R[j], R[4 + j], R[8 + j]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dS[i * 3 + j] = dot3(R[i], R[4 + i], R[8 + i], dCR[j], dCR[3 + j], dCR[6 + j]);
 #pragma unroll
     for (int k = 0; k < 9; ++k) out(kOutCov, g, k, dS[k], 0.f);
     return;
   }
-  // raw path: Sigma = M M^T, M = R(q) diag(s), s = exp(scaling), q = normalize(rotation)
-  const float *sc = kHot ? scl_pre : a.g.scaling + (int64_t)g * 3, *rq = kHot ? rot_pre : a.g.rotation + (int64_t)g * 4;
-  float qn = sqrtf(dot3(rq[0], rq[1], rq[2], rq[0], rq[1], rq[2]) + rq[3] * rq[3]);
-  qn = qn < 1e-12f ? 1e-12f : qn;
-  const float iq = 1.f / qn;
-  const float w = rq[0] * iq, x = rq[1] * iq, y = rq[2] * iq, z = rq[3] * iq;
-  const float Rq[9] = {1.f - 2.f * (y * y + z * z), 2.f * (x * y - w * z), 2.f * (x * z + w * y),
-                       2.f * (x * y + w * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - w * x),
-                       2.f * (x * z - w * y), 2.f * (y * z + w * x), 1.f - 2.f * (x * x + y * y)};
-  const float s3[3] = {expf(sc[0]), expf(sc[1]), expf(sc[2])};
-  float Ss[9];  // dS + dS^T
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Ss[i * 3 + k] = dS[i * 3 + k] + dS[k * 3 + i];
-  float dR[9];  // dL/dRq = (dS + dS^T) Rq diag(s)^2
+  // raw path: Sigma = Rq diag(s^2) Rq^T, s = exp(scaling), q = normalize(rotation).
+  // In the Gaussian's own frame, with P = J Rv Rq (2x3) and M = P^T (dV + dV^T) P
+  // = Rq^T (dS + dS^T) Rq:  dL/dscaling_j = M_jj s_j^2, and a rotation of the
+  // frame by d_omega changes L by sum_k g_k d_omega_k, g = (M_12 (s_1^2 - s_2^2),
+  // M_02 (s_2^2 - s_0^2), M_01 (s_0^2 - s_1^2)) -- the differences of the scales
+  // formed as s_j^2 expm1(2 (scaling_i - scaling_j)), so that two nearly equal
+  // axes do not cancel.  d_omega = 2 vec(conj(q) dq) for a unit q gives
+  // dL/dq = 2 q (0, g), a tangent of the sphere, and 1 / |rotation| chains
+  // through the normalisation.
+  double B[9], P[6];  // B = Rv Rq
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-      dR[i * 3 + j] = dot3(Ss[i * 3], Ss[i * 3 + 1], Ss[i * 3 + 2], Rq[j], Rq[3 + j], Rq[6 + j]) * (s3[j] * s3[j]);
+      B[i * 3 + j] = (double)R[i * 4] * Rqd[j] + (double)R[i * 4 + 1] * Rqd[3 + j] + (double)R[i * 4 + 2] * Rqd[6 + j];
 #pragma unroll
-  for (int j = 0; j < 3; ++j)  // dL/ds_j s_j: (dR / s_j) . Rq column j, times s_j
-    out(kOutScaling, g, j, dot3(dR[j], dR[3 + j], dR[6 + j], Rq[j], Rq[3 + j], Rq[6 + j]), sc[j]);
-  const float dw = 2.f * ((-z * dR[1] + y * dR[2]) + (z * dR[3] - x * dR[5]) + (-y * dR[6] + x * dR[7]));
-  const float dx = 2.f * ((y * dR[1] + z * dR[2]) + (y * dR[3] - 2.f * x * dR[4]) + (-w * dR[5] + z * dR[6]) +
-                          (w * dR[7] - 2.f * x * dR[8]));
-  const float dy = 2.f * ((-2.f * y * dR[0] + x * dR[1]) + (w * dR[2] + x * dR[3]) + (z * dR[5] - w * dR[6]) +
-                          (z * dR[7] - 2.f * y * dR[8]));
-  const float dz = 2.f * ((-2.f * z * dR[0] - w * dR[1]) + (x * dR[2] + w * dR[3]) + (-2.f * z * dR[4] + y * dR[5]) +
-                          (x * dR[6] + y * dR[7]));
-  const float dot = __builtin_fmaf(dw, w, __builtin_fmaf(dx, x, __builtin_fmaf(dy, y, dz * z)));
-  out(kOutRotation, g, 0, (dw - w * dot) * iq, rq[0]);
-  out(kOutRotation, g, 1, (dx - x * dot) * iq, rq[1]);
-  out(kOutRotation, g, 2, (dy - y * dot) * iq, rq[2]);
-  out(kOutRotation, g, 3, (dz - z * dot) * iq, rq[3]);
+  for (int j = 0; j < 3; ++j) {
+    P[j] = Jd[0] * B[j] + Jd[2] * B[6 + j];
+    P[3 + j] = Jd[4] * B[3 + j] + Jd[5] * B[6 + j];
+  }
+  const double va = 2.0 * dVd[0], vb = dVd[1] + dVd[2], vc = 2.0 * dVd[3];  // dV + dV^T
+  double T0[3], T1[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    T0[j] = va * P[j] + vb * P[3 + j];
+    T1[j] = vb * P[j] + vc * P[3 + j];
+  }
+  auto Mij = [&](int i, int j) { return P[i] * T0[j] + P[3 + i] * T1[j]; };
+#pragma unroll
+  for (int j = 0; j < 3; ++j) out(kOutScaling, g, j, (float)(Mij(j, j) * s2d[j]), sc[j]);
+  auto dd = [&](int i, int j) { return s2d[j] * (double)expm1f(2.f * (sc[i] - sc[j])); };  // s_i^2 - s_j^2
+  const double g0 = Mij(1, 2) * dd(1, 2), g1 = Mij(0, 2) * dd(2, 0), g2 = Mij(0, 1) * dd(0, 1);
+  const double w = qd[0], x = qd[1], y = qd[2], z = qd[3], k2 = 2.0 * iqd;
+  out(kOutRotation, g, 0, (float)(k2 * (-x * g0 - y * g1 - z * g2)), rq[0]);
+  out(kOutRotation, g, 1, (float)(k2 * (w * g0 + y * g2 - z * g1)), rq[1]);
+  out(kOutRotation, g, 2, (float)(k2 * (w * g1 + z * g0 - x * g2)), rq[2]);
+  out(kOutRotation, g, 3, (float)(k2 * (w * g2 + x * g1 - y * g0)), rq[3]);
 }
 
 // kHot: partials present, no viewspace/conic cotangents, raw scale/rotation,
