@@ -370,6 +370,107 @@ int64_t gs_blend_backward_groups(int32_t tiles_x, int32_t tiles_y, int32_t cell_
 gs_status gs_blend_backward_lane_stats(const gs_blend_bwd_args *a, uint64_t *hist, uint32_t *per_group,
                                        gs_stream_t stream);
 
+/* ---- Per-Gaussian feature channels through the blend ----------------------
+ * features_out[k, p] = sum_i c_i F[g_i, k] over the entries i of pixel p's
+ * tile list that the colour forward accepted, with the colour forward's own
+ * contribution weights c_i (renderer.py:319-353: w = clamp(exp(-s/2), 0, 1),
+ * skipped below 1e-5; alpha = clamp(o w, 0, 1); c = (1 - A) alpha; A += c,
+ * break once A >= 0.995).  No background, clamp, sigmoid or normalisation: a
+ * pixel no entry reaches gets 0.  The kernels evaluate no transmittance chain
+ * of their own: they replay the decisions of the gs_blend_forward that wrote
+ * ranges / sorted_gauss / records / cell_neval / live_bits, bit for bit, as
+ * gs_blend_backward does (one 64-lane workgroup per (tile, 8x8 cell), any
+ * tile_size; live_bits NULL: every entry of a cell's evaluated prefix).
+ * Channels go in chunks of GS_FEATURE_CHUNK = 4, the payload width of the
+ * colour pass (r, g, b, z), so a chunk's backward fits the 40-byte partial
+ * and everything behind it.  `features` is the [n, C] input staged
+ * chunk-major, [ceil(C / 4), n, 4] with the last chunk zero-padded: one
+ * aligned 16-byte load per (entry, chunk).
+ * GS_MAX_FEATURE_CHANNELS bounds C: 64 chunks, the forward's grid y axis, and
+ * as many backward launches per cell batch -- wide enough for distilled
+ * feature fields (CLIP / DINO embeddings are rendered at 16..256 channels),
+ * small enough that a mistaken shape ([N, H W]) is refused, not launched. */
+#define GS_FEATURE_CHUNK 4
+#define GS_MAX_FEATURE_CHANNELS 256
+typedef struct gs_feature_fwd_args {
+  gs_camera cam;                /* the colour forward's (bg is not read) */
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;       /* as gs_blend_fwd_args, after that forward */
+  const uint32_t *sorted_gauss;
+  const float *records;
+  const uint32_t *cell_neval;   /* gs_blend_fwd_args.cell_neval, as written */
+  const uint64_t *live_bits;    /* gs_blend_fwd_args.live_bits, as written, or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;        /* n: the rows of a staged chunk */
+  int32_t channels;             /* C in 1..GS_MAX_FEATURE_CHANNELS */
+  const float *features;        /* [ceil(C/4), n, 4] staged, 16-byte aligned */
+  float *out;                   /* [C, H, W]: every pixel written */
+} gs_feature_fwd_args;
+/* Every chunk in one launch (chunks on the grid's y axis). */
+gs_status gs_blend_features_forward(const gs_feature_fwd_args *a, gs_stream_t stream);
+
+/* Backward of one chunk over one cell batch, for a cotangent g_out [C, H, W].
+ * With X_i = sum_k g_out[k,p] F[g_i,k], K = sum_k g_out[k,p] out[k,p] and
+ * P_i = sum_{j<=i} c_j X_j (k over the chunk's channels; the chunks add):
+ *   dL/dF[g, k]  = sum_{p, i: g_i = g} c_i g_out[k, p]
+ *   dL/dalpha_i  = T_i (X_i + (P_i - K) / T_{i+1})   (the terminating entry: T_i X_i)
+ * chained into (dmu_x, dmu_y, dQ00, dQ01, dQ11, d_opacity) with the clamp
+ * masks of gs_blend_backward -- its formula with bg = 0, no alpha cotangent,
+ * no pixel clamp and a plain fourth channel where it has depth.  Writes one
+ * partial per replayed (entry, cell) in gs_blend_backward's layout,
+ * pair_grads[G e + q] = {dmu_x, dmu_y, dQ00, dQ01, dQ11, d_opacity, dF0, dF1,
+ * dF2, dF3}, and sets slot_live[G e + q] = 1 (G = cell_count, q the cell's
+ * index in the batch, e the entry's gradient slot).  No atomics. */
+typedef struct gs_feature_bwd_args {
+  gs_camera cam;
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;
+  const uint32_t *sorted_gauss;
+  const float *records;         /* with pair offsets (gs_bin_emit) */
+  const uint32_t *cell_neval;
+  const uint64_t *live_bits;    /* or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;
+  int32_t channels;             /* C */
+  int32_t chunk;                /* 0 .. ceil(C/4) - 1: channels [4 chunk, 4 chunk + 4) */
+  const float *features;        /* the forward's staged input */
+  const float *out;             /* [C, H, W] the forward's output, unmodified */
+  const float *g_out;           /* [C, H, W] dL/dout */
+  float *pair_grads;            /* [T, G, GS_PARTIAL_STRIDE] */
+  uint8_t *slot_live;           /* [T, G], zeroed by the caller */
+  int32_t cell_begin;           /* the batch's first cell */
+  int32_t cell_count;           /* the batch's cells (0 with cell_begin 0: the whole tile) */
+} gs_feature_bwd_args;
+gs_status gs_blend_features_backward(const gs_feature_bwd_args *a, gs_stream_t stream);
+
+/* The gather of a feature chunk's partials: per Gaussian g, its slots' live
+ * partials summed in gs_gather_partials' order (the same lanes per Gaussian,
+ * slot and group order and lane tree).  Values 0..5 go to grad_sums[g, 0..5]:
+ * stored, with grad_sums[g, 6..9] zeroed, when accumulate = 0; added, 6..9
+ * left alone, when accumulate = 1 (the colour pass's sums, or an earlier
+ * chunk's or batch's, are there).  Values 6..9 go to d_features[g,
+ * channel_begin .. channel_begin + channel_count): stored when
+ * feature_accumulate = 0 (a chunk's first cell batch), added when 1. */
+typedef struct gs_feature_gather_args {
+  int32_t n;
+  const uint8_t *vis;           /* as gs_project_bwd_args */
+  const uint32_t *rects;
+  const uint32_t *pair_offset;
+  const float *pair_grads;      /* [T, G, GS_PARTIAL_STRIDE] */
+  const uint8_t *slot_live;     /* [T, G] */
+  int32_t partial_groups;       /* G */
+  int32_t accumulate;
+  float *grad_sums;             /* [n, GS_PAIR_GRAD_FLOATS] */
+  float *d_features;            /* [n, d_features_stride] */
+  int64_t d_features_stride;    /* floats between rows */
+  int32_t channel_begin;
+  int32_t channel_count;        /* 1..GS_FEATURE_CHUNK */
+  int32_t feature_accumulate;
+} gs_feature_gather_args;
+gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_t stream);
+
 /* ---- Backward of the projection ----------------------------------------
  * Sums each Gaussian's slot partials (slots [pair_offset[g], pair_offset[g]
  * + touches), the groups slot_live flags), adds cotangents on the viewspace_points /

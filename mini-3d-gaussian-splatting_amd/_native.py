@@ -111,6 +111,38 @@ class GsProjectBwdArgs(C.Structure):
     ]
 
 
+GS_FEATURE_CHUNK = 4  # channels per feature chunk: the colour pass's payload width (r, g, b, z)
+GS_MAX_FEATURE_CHANNELS = 256
+
+
+class GsFeatureFwdArgs(C.Structure):
+    _fields_ = [
+        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
+        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
+        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("channels", C.c_int32), ("features", _vp), ("out", _vp),
+    ]
+
+
+class GsFeatureBwdArgs(C.Structure):
+    _fields_ = [
+        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
+        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
+        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("channels", C.c_int32), ("chunk", C.c_int32), ("features", _vp), ("out", _vp), ("g_out", _vp),
+        ("pair_grads", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32), ("cell_count", C.c_int32),
+    ]
+
+
+class GsFeatureGatherArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("vis", _vp), ("rects", _vp), ("pair_offset", _vp), ("pair_grads", _vp),
+        ("slot_live", _vp), ("partial_groups", C.c_int32), ("accumulate", C.c_int32), ("grad_sums", _vp),
+        ("d_features", _vp), ("d_features_stride", C.c_int64), ("channel_begin", C.c_int32),
+        ("channel_count", C.c_int32), ("feature_accumulate", C.c_int32),
+    ]
+
+
 GS_POSE_ROW = 16  # doubles per row of gs_project_pose_args.pose_partials; one row per 256 Gaussians
 GS_POSE_BLOCK = 256
 
@@ -209,6 +241,7 @@ EXPORTS = (
     "gs_blend_backward_groups", "gs_blend_backward_lane_stats", "gs_gather_partials", "gs_frame_workspace_bytes", "gs_tile_workspace_bytes", "gs_render_forward",
     "gs_render_backward", "gs_frame_offsets", "gs_tile_offsets", "gs_adam_step", "gs_project_backward_adam", "gs_loss_workspace_bytes", "gs_loss_forward", "gs_loss_backward",
     "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit",
+    "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
 )
 
 _lib = None
@@ -269,9 +302,13 @@ def _declare(lib):
     lib.gs_densify_workspace_bytes.restype = C.c_size_t
     lib.gs_densify_count.argtypes = [P(GsDensifyArgs), _vp]
     lib.gs_densify_emit.argtypes = [P(GsDensifyArgs), _vp]
+    lib.gs_blend_features_forward.argtypes = [P(GsFeatureFwdArgs), _vp]
+    lib.gs_blend_features_backward.argtypes = [P(GsFeatureBwdArgs), _vp]
+    lib.gs_gather_feature_partials.argtypes = [P(GsFeatureGatherArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
-              "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit"):
+              "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
+              "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials"):
         getattr(lib, f).restype = C.c_int
 
 
@@ -285,6 +322,13 @@ def load(path: str = LIB_PATH):
                     f"{LIB_NAME} not found at {path}; build it with "
                     "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950)")
             lib = C.CDLL(path)
+            # (exports added without an ABI bump: a library built before them has the
+            # same version number, and ctypes would only say AttributeError)
+            missing = [name for name in EXPORTS if not hasattr(lib, name)]
+            if missing:
+                raise NativeLibraryError(
+                    f"{LIB_NAME} at {path} is out of date: it lacks {', '.join(missing)}; rebuild it with "
+                    "`python -c 'import __graft_entry__ as g; g.build()'`")
             _declare(lib)
             v = lib.gs_abi_version()
             if v != GS_ABI_VERSION:

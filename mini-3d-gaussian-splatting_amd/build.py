@@ -16,7 +16,7 @@ ROOT = os.path.dirname(HERE)
 # The one list of the library's sources (tools/*.sh take it from --print-sources;
 # tests/test_abi.py checks it against the csrc/ and include/ directories).
 SRC = [os.path.join(HERE, "csrc", n) for n in (
-    "gs_common.hip", "gs_project.hip", "gs_sort.hip", "gs_bin.hip", "gs_blend.hip", "gs_adam.hip",
+    "gs_common.hip", "gs_project.hip", "gs_sort.hip", "gs_bin.hip", "gs_blend.hip", "gs_features.hip", "gs_adam.hip",
     "gs_loss.hip", "gs_densify.hip", "gs_render.hip")]
 HDR = [os.path.join(ROOT, "include", "gsplat_mi355x.h"), os.path.join(HERE, "csrc", "gs_internal.h"),
        os.path.join(HERE, "csrc", "gs_device.h")]

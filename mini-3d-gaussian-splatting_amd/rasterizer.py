@@ -669,8 +669,11 @@ def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opa
 
 def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
                      sh_rest=None, sh_degree=0, pair_counts=None, depth_window_ok=True, need_grad=False,
-                     pix_neval=None):
-    """pair_counts / pix_neval: optional int32 [H*W] the blend fills with each
+                     pix_neval=None, stage_path=False):
+    """stage_path: take the stage-by-stage path below at the default tile too
+    (the feature pass reads the frame's buffers as tensors; the two paths'
+    outputs and gradients are bit-identical).
+    pair_counts / pix_neval: optional int32 [H*W] the blend fills with each
     pixel's contributing pairs / evaluated entries (measurement counters,
     SURVEY 8d, and the oracle's decision-forced replay; not in render()).
 
@@ -679,7 +682,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
     per 8 bits, gs_project_args.key_base); this frame's range, read back with
     (M, T), says whether the window held -- if not, the frame is rendered
     again with full 32-bit keys (depth_window_ok=False)."""
-    if _FRAME_CALLS and cam.tile_size == N.GS_DEFAULT_TILE:
+    if _FRAME_CALLS and cam.tile_size == N.GS_DEFAULT_TILE and not stage_path:
         hc = _host_counters(xyz.device)
         if hc.dptr is not None:
             return _forward_frame(cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest,
@@ -770,7 +773,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
             _frame_missed(dev, zmax, T)
             return forward_pipeline(cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit,
                                     sh_rest, sh_degree, pair_counts, depth_window_ok=False, need_grad=need_grad,
-                                    pix_neval=pix_neval)
+                                    pix_neval=pix_neval, stage_path=stage_path)
     else:
         M, T = 0, 0
     fr.M, fr.T = M, T
@@ -828,9 +831,12 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
 def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotation, logits, opacity,
                       means2d, conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit=False,
-                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None):
+                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None, feat=None):
     """outputs: the forward's (image, alpha, depth), unmodified -- with the
     frame's clamp flags they are the blend backward's per-pixel state.
+    feat: optional _FeaturePass with a cotangent on the feature image (a
+    stage-path frame): its chunks' geometry sums are added to the colour
+    pass's before the one projection backward, and feat.d_features is set.
     d_view: optional fp32 [12] on the device -- the projection backward then
     runs as gs_project_backward_pose, one range over every Gaussian, and
     writes dL/d(view rows [R | t]) there (the per-Gaussian gradients are the
@@ -897,7 +903,13 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     gm = None if g_means2d is None else g_means2d.contiguous()
     gc = None if g_conics is None else g_conics.contiguous()
     gst = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
-    if pair_grads is not None and fr.groups < cam.groups:
+    if feat is not None and fr.M > 0 and fr.T > 0:
+        # (the colour pass's sums first -- gathered here when its one batch left them as
+        # partials -- then every feature chunk's added: one projection backward over the total)
+        colour_sums = batch_sums if (pair_grads is not None and fr.groups < cam.groups) else None
+        grad_sums = _feature_backward(lib, cam, fr, feat, n, pair_grads, slot_live, colour_sums, s)
+        pair_grads = slot_live = None
+    elif pair_grads is not None and fr.groups < cam.groups:
         grad_sums, pair_grads, slot_live = batch_sums, None, None  # (summed batch by batch above)
     else:
         grad_sums = None if pair_grads is None else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
@@ -1073,6 +1085,167 @@ def _rows_of(pb: "N.GsProjectBwdArgs", lo: int, hi: int) -> "N.GsProjectBwdArgs"
     return r
 
 
+class _FeaturePass:
+    """One backward's view of a frame's feature pass: the staged input, the
+    forward's feature image, its cotangent, and the result d_features [n, C]."""
+    __slots__ = ("staged", "out", "g_out", "channels", "d_features")
+
+    def __init__(self, staged, out, g_out, channels):
+        self.staged, self.out, self.g_out, self.channels, self.d_features = staged, out, g_out, channels, None
+
+
+def _feature_chunks(channels: int) -> int:
+    return (channels + N.GS_FEATURE_CHUNK - 1) // N.GS_FEATURE_CHUNK
+
+
+def _stage_features(features: torch.Tensor) -> torch.Tensor:
+    """[n, C] fp32 -> [ceil(C/4), n, 4] contiguous, the last chunk zero-padded:
+    the kernels read a chunk's payload as one aligned 16-byte load per entry
+    (rows of a [n, C] tensor are 16-byte aligned only when C % 4 == 0, and a
+    chunk's rows would be C floats apart).  A torch pad + transpose copy."""
+    n, c = features.shape
+    k = _feature_chunks(c)
+    f = features.detach()
+    if c != k * N.GS_FEATURE_CHUNK:
+        f = torch.nn.functional.pad(f, (0, k * N.GS_FEATURE_CHUNK - c))
+    return f.reshape(n, k, N.GS_FEATURE_CHUNK).permute(1, 0, 2).contiguous()
+
+
+def _feature_forward(cam: CameraParams, fr: _Frame, staged: torch.Tensor, channels: int, n: int, dev) -> torch.Tensor:
+    """The feature image [C, H, W] of a stage-path frame: gs_blend_features_forward
+    over the state the colour forward left in `fr` (zeros when nothing was drawn)."""
+    H, W = int(cam.image_height), int(cam.image_width)
+    if fr.M == 0 or fr.T == 0:
+        return torch.zeros((channels, H, W), dtype=torch.float32, device=dev)
+    out = torch.empty((channels, H, W), dtype=torch.float32, device=dev)
+    fa = N.GsFeatureFwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                            N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
+                            0 if fr.live_bits is None else fr.live_bits.shape[1], fr.T, n, channels,
+                            N.ptr(staged), N.ptr(out))
+    StageTimer.mark("features_fwd")
+    N.check(N.load().gs_blend_features_forward(C.byref(fa), _stream()), "gs_blend_features_forward")
+    StageTimer.mark("~end_features_fwd")
+    return out
+
+
+def _feature_backward(lib, cam: CameraParams, fr: _Frame, feat: _FeaturePass, n: int, pair_grads, slot_live,
+                      colour_sums, s) -> torch.Tensor:
+    """The feature pass's backward over a stage-path frame: per chunk and cell
+    batch (the frame's own plan: fr.groups cells at a time) the blend backward
+    of that chunk and its gather -- geometry sums added to grad_sums, the
+    chunk's columns of feat.d_features stored by a chunk's first batch and
+    added to by the later ones.  Returns grad_sums [n, 10] for the projection
+    backward.  pair_grads / slot_live: the colour pass's one-batch partials,
+    not yet gathered (gathered here first, then the buffer is reused), or
+    None; colour_sums: its sums when it ran in batches, or None.  The flags
+    are this call's own scratch, cleared before every launch."""
+    dev = feat.out.device
+    f32 = torch.float32
+    G, Q, T, Cn = fr.groups, cam.cells, fr.T, feat.channels
+    ga = N.GsProjectBwdArgs()
+    have = colour_sums is not None
+    grad_sums = colour_sums if have else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
+    if pair_grads is not None and not have:
+        ga.g.n = n
+        ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
+        ga.pair_grads, ga.slot_live, ga.grad_sums = N.ptr(pair_grads), N.ptr(slot_live), N.ptr(grad_sums)
+        ga.partial_groups = G
+        N.check(lib.gs_gather_partials(C.byref(ga), 0, s), "gs_gather_partials")
+        have = True
+    if pair_grads is None or pair_grads.shape[0] < T * G:
+        pair_grads = torch.empty((T * G, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
+    flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
+    g_out = feat.g_out
+    if g_out.dtype != f32 or not g_out.is_contiguous():
+        g_out = g_out.to(f32).contiguous()
+    d_features = torch.empty((n, Cn), dtype=f32, device=dev)
+    ba = N.GsFeatureBwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                            N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
+                            0 if fr.live_bits is None else fr.live_bits.shape[1], T, n, Cn, 0, N.ptr(feat.staged),
+                            N.ptr(feat.out), N.ptr(g_out), N.ptr(pair_grads), N.ptr(flags), 0, 0)
+    fg = N.GsFeatureGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(pair_grads),
+                               N.ptr(flags), G, 0, N.ptr(grad_sums), N.ptr(d_features), d_features.stride(0), 0, 0, 0)
+    StageTimer.mark("features_bwd")
+    for chunk in range(_feature_chunks(Cn)):
+        ba.chunk = chunk
+        fg.channel_begin = chunk * N.GS_FEATURE_CHUNK
+        fg.channel_count = min(N.GS_FEATURE_CHUNK, Cn - fg.channel_begin)
+        for b, c0 in enumerate(range(0, Q, G)):
+            ba.cell_begin, ba.cell_count = c0, min(G, Q - c0)
+            fg.partial_groups = ba.cell_count
+            fg.accumulate, fg.feature_accumulate = (1 if have else 0), (1 if b else 0)
+            flags.zero_()
+            N.check(lib.gs_blend_features_backward(C.byref(ba), s), "gs_blend_features_backward")
+            N.check(lib.gs_gather_feature_partials(C.byref(fg), s), "gs_gather_feature_partials")
+            have = True
+    StageTimer.mark("~end_features_bwd")
+    feat.d_features = d_features
+    return grad_sums
+
+
+class RasterizeGaussianFeatures(torch.autograd.Function):
+    """RasterizeGaussians with one more differentiable input, features [N, C],
+    and one more output, the feature image [C, H, W] composited with the
+    colour pass's own weights.  The frame is the stage path's (the feature
+    kernels read its buffers); the seven other outputs, and their gradients
+    when the feature image takes no part in the loss, are RasterizeGaussians'
+    bit for bit."""
+
+    @staticmethod
+    def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, cam: CameraParams,
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None):
+        image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
+            cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
+            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=True)
+        n, channels = int(features.shape[0]), int(features.shape[1])
+        staged = _stage_features(features)
+        feat_image = _feature_forward(cam, fr, staged, channels, n, xyz.device)
+        ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
+        ctx.grad_dest = grad_dest
+        ctx.feature_shape = (n, channels)
+        ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[12] else None
+        ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
+                              depth, staged, feat_image)
+        ctx.mark_non_differentiable(radii, vis)
+        ctx.set_materialize_grads(False)
+        return image, alpha, depth, means2d, conics, radii, vis, feat_image
+
+    @staticmethod
+    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, g_features):
+        (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth, staged,
+         feat_image) = ctx.saved_tensors
+        g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
+        dest = ctx.grad_dest() if ctx.grad_dest is not None else None
+        d_view = None
+        if ctx.view_shape is not None:
+            d_view = torch.empty((12,), dtype=torch.float32, device=xyz.device)
+        # (no cotangent on the feature image: RasterizeGaussians' backward, launch for launch)
+        feat = None if g_features is None else _FeaturePass(staged, feat_image, g_features, ctx.feature_shape[1])
+        d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
+            ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
+            g_image, g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
+            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, feat=feat)
+        need = ctx.needs_input_grad
+        d_features = None
+        if need[7] and feat is not None:
+            d_features = feat.d_features
+            if d_features is None:  # (nothing drawn: no entry carries the cotangent anywhere)
+                d_features = torch.zeros(ctx.feature_shape, dtype=torch.float32, device=xyz.device)
+        g_view = None
+        if d_view is not None:
+            g_view = d_view.view(3, 4)
+            if ctx.view_shape == (4, 4):
+                g_view = torch.cat([g_view, g_view.new_zeros((1, 4))], 0)
+        return (d_xyz if need[0] else None,
+                d_cov if (cov3d is not None and need[1]) else None,
+                d_scl if (scaling is not None and need[2]) else None,
+                d_rot if (rotation is not None and need[3]) else None,
+                d_col.view(logits.shape) if need[4] else None,
+                d_op.view(opacity.shape) if need[5] else None,
+                d_sh if (sh_rest is not None and need[6]) else None,
+                d_features, None, None, None, None, g_view)
+
+
 class RasterizeGaussians(torch.autograd.Function):
     """Differentiable render: inputs are the model accessors' tensors, outputs
     are (image, alpha, depth, viewspace_points, conics, radii, visibility)."""
@@ -1126,8 +1299,13 @@ class RasterizeGaussians(torch.autograd.Function):
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
-              sh_rest=None, sh_degree=0, grad_dest=None, view=None):
-    """opacity_is_logit: opacity holds the model's raw _opacity and the kernels
+              sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None):
+    """features: optional floating-point [N, C] tensor on the Gaussians' device,
+    C in 1..GS_MAX_FEATURE_CHANNELS: an eighth output follows the seven, the
+    feature image [C, H, W] fp32 = sum_i c_i features[g_i] per pixel with the
+    colour pass's own weights c_i (no background, clamp or normalisation);
+    differentiable in the features and in the geometry (and `view`).
+    opacity_is_logit: opacity holds the model's raw _opacity and the kernels
     apply get_opacity's sigmoid (fused; its gradient goes to the logit).
     sh_degree > 0: view-dependent colour from sh_rest ([N,15,3] rest
     coefficients, e.g. get_features[:,1:,:]); 0 is the reference's DC-only
@@ -1164,6 +1342,15 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     rotation = prep("rotation", rotation, (4,))
     logits = prep("colour", logits, (3,))
     opacity = prep("opacity", opacity, (1,))
+    if features is not None:
+        if not isinstance(features, torch.Tensor):
+            raise TypeError(f"features must be a tensor, got {type(features).__name__}")
+        if features.dim() != 2:
+            raise ValueError(f"features must be [N, C], got {tuple(features.shape)}")
+        if not 1 <= features.shape[1] <= N.GS_MAX_FEATURE_CHANNELS:
+            raise ValueError(f"features must have 1..{N.GS_MAX_FEATURE_CHANNELS} channels "
+                             f"(GS_MAX_FEATURE_CHANNELS), got {features.shape[1]}")
+        features = prep("features", features, (features.shape[1],))
     if cov3d is None and (scaling is None or rotation is None):
         raise ValueError("need a covariance or scaling + rotation")
     sh_degree = int(sh_degree)
@@ -1188,6 +1375,9 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     logits, _ = _rows(logits, 3)
     opacity, _ = _rows(opacity, 1)
     if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
+        if features is not None:
+            return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
+                                                   cam, bool(opacity_is_logit), sh_degree, grad_dest)
         return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
                                         bool(opacity_is_logit), sh_degree, grad_dest)
     if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
@@ -1195,5 +1385,8 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     # (differentiable, as the reference's .to(device): the gradient returns to
     # the caller's device and dtype)
     view = view.to(device=xyz.device, dtype=torch.float32)
+    if features is not None:
+        return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
+                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, view)
     return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
                                     bool(opacity_is_logit), sh_degree, grad_dest, view)

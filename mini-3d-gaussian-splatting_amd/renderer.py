@@ -24,6 +24,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     plain tensor nothing about the render changes.
   * `settings.scale_modifier` and `settings.debug` are ignored, as in the
     reference.
+  * `render(..., features=F)` (not in the reference) also returns
+    "features": F [N, C] composited with the colour pass's own weights.
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
     switches on view-dependent SH colour; at 0 -- the default for the
     reference's own model and stubs -- colours are the reference's
@@ -126,7 +128,16 @@ class GaussianRenderer:
         self.radius_max = radius_max
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
-    def render(self, camera, gaussians, settings: RenderSettings) -> Dict[str, torch.Tensor]:
+    def render(self, camera, gaussians, settings: RenderSettings,
+               features: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """features: optional floating-point [N, C] per-Gaussian values
+        (normals, embeddings, positions, ...) on the Gaussians' device.  The
+        result then also holds "features" [C, H, W] fp32: each pixel's
+        sum_i c_i features[g_i] with exactly the weights c_i the colour pass
+        gave its contributors -- no sigmoid, clamp, background or
+        normalisation (a feature background b is the caller's
+        out["features"] + (1 - out["alpha"]) * b).  Gradients reach the
+        features and, through the weights, the geometry and the pose."""
         wv = _world_view(camera)
         cam = camera_params(camera, settings, self.radius_min, self.radius_max, self.tile_size, world_view=wv)
         # a view on the autograd tape receives its gradient (the reference's
@@ -182,9 +193,12 @@ class GaussianRenderer:
                 if hasattr(sink, "rows_ready") and getattr(sink, "covers", lambda _: False)(leaves):
                     d["_rows_ready"], d["_chunks"] = sink.rows_ready, sink.overlap_chunks()
                 return d
-        image, alpha, depth, means2d, conics, radii, vis = rasterize(
+        extra = dict(pose)
+        if features is not None:
+            extra["features"] = features
+        image, alpha, depth, means2d, conics, radii, vis, *feature_image = rasterize(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
-            sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **pose)
+            sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **extra)
         # the reference's output dtypes (renderer.py:74-83, :273-275, :359-367):
         # the projection outputs in the Gaussians' dtype, image in the
         # background's (out_rgb starts as bg), alpha / depth float32 (zeros of
@@ -193,7 +207,7 @@ class GaussianRenderer:
             means2d, conics, radii = means2d.double(), conics.double(), radii.double()
         if torch.as_tensor(settings.bg_color).dtype == torch.float64:
             image = image.double()
-        return {
+        out = {
             "image": image,
             "alpha": alpha,
             "depth": depth,
@@ -202,3 +216,6 @@ class GaussianRenderer:
             "radii": radii,
             "conics": conics,
         }
+        if feature_image:
+            out["features"] = feature_image[0]
+        return out
