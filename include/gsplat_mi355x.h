@@ -636,7 +636,48 @@ gs_status gs_loss_backward(const gs_loss_args *a, gs_stream_t stream);
  * these: _append_points reads a missing `_scaling_log` (:229).)  Two
  * phases: gs_densify_count writes counters, the caller sizes the outputs
  * (n_out = 0, everything pruned: there is nothing to emit, and
- * gs_densify_emit refuses the NULL outputs an empty allocation has). */
+ * gs_densify_emit refuses the NULL outputs an empty allocation has).
+ *
+ * Screen-space criterion (the 3DGS one; every field below is a trailing one,
+ * all zero: the behaviour above, bit for bit).  With grad_accum / grad_denom
+ * (the statistics gs_density_accumulate keeps) the gradient test reads
+ *   g = grad_denom[i] > 0 ? grad_accum[i] / grad_denom[i] : 0
+ * -- the mean over the views that saw i of the NDC-unit norm of the gradient
+ * at its projected centre -- in place of |dL/dxyz_i|; a Gaussian no view saw
+ * is never hot.  xyz_grad together with grad_accum, or grad_accum without
+ * grad_denom, is GS_ERR_INVALID_ARG.  With GS_DENSIFY_PRUNE, max_radii given
+ * and max_screen_radius > 0, big = max_radii[i] > max_screen_radius, and an
+ * original that is big and not split produces no output: keep = !split and
+ * alive and !big, clone = clone and alive and !big.  A split's children are
+ * new and smaller: unaffected.  Split geometry, clone jitter, output order,
+ * moment remap and counters are as above either way.
+ *
+ * gs_density_accumulate adds one rendered view to those statistics, after
+ * that view's backward: one launch, one thread per Gaussian, no atomics.  For
+ * every g < n with vis[g] != 0, with W, H the rendered image's size,
+ *   gx = (grad_sums ? grad_sums[g * GS_PAIR_GRAD_FLOATS + 0] : 0) + (g_means2d ? g_means2d[2g]     : 0)
+ *   gy = (grad_sums ? grad_sums[g * GS_PAIR_GRAD_FLOATS + 1] : 0) + (g_means2d ? g_means2d[2g + 1] : 0)
+ *   grad_accum[g] += sqrtf((0.5f W gx)^2 + (0.5f H gy)^2)
+ *   denom[g]      += 1
+ *   max_radii[g]   = fmaxf(max_radii[g], radii[g])
+ * (0.5 W, 0.5 H: a per-pixel gradient in the NDC units the 3DGS threshold is
+ * defined for).  grad_sums is what the blend backward's gather leaves -- the
+ * blend's dL/dmeans2d in columns 0..1 -- or NULL for a frame without a blend
+ * gradient; g_means2d is the caller's own cotangent on means2d, or NULL.  A
+ * row with vis[g] == 0 is neither read nor written: its three values keep
+ * their bits.  n == 0: GS_OK, nothing launched; a NULL required pointer or a
+ * non-positive size: GS_ERR_INVALID_ARG before any HIP call. */
+typedef struct gs_density_stats_args {
+  int32_t n;
+  int32_t image_width, image_height; /* gs_camera.image_width / image_height of the rendered view */
+  const uint8_t *vis;                /* [n] the forward's visibility */
+  const float *radii;                /* [n] the forward's radii */
+  const float *grad_sums;            /* [n, GS_PAIR_GRAD_FLOATS], or NULL */
+  const float *g_means2d;            /* [n, 2], or NULL */
+  float *grad_accum, *denom, *max_radii; /* [n] each, read-modify-written where visible */
+} gs_density_stats_args;
+gs_status gs_density_accumulate(const gs_density_stats_args *a, gs_stream_t stream);
+
 #define GS_DENSIFY_SPLIT 1
 #define GS_DENSIFY_CLONE 2
 #define GS_DENSIFY_PRUNE 4
@@ -652,7 +693,7 @@ typedef struct gs_densify_args {
   int32_t n;
   int32_t rest_floats;
   gs_model_arrays in;             /* read only */
-  const float *xyz_grad;          /* [n,3], or NULL: nothing is split or cloned */
+  const float *xyz_grad;          /* [n,3], or NULL: nothing is split or cloned (unless grad_accum is given) */
   float grad_threshold, scene_extent;
   float split_size, clone_size;   /* 0.03, 0.01 (gaussian_model.py:137,166) */
   float min_opacity;              /* 0.01 (optimizer.py:64) */
@@ -663,6 +704,10 @@ typedef struct gs_densify_args {
   size_t workspace_bytes;
   uint32_t *counters;             /* [4]: kept, split children per side, clones, n_out */
   gs_model_arrays out, adam_m_out, adam_v_out;
+  /* the screen-space criterion (above); all zero: |xyz_grad| and no radius prune */
+  const float *grad_accum, *grad_denom; /* [n] each: the gradient test reads their quotient */
+  const float *max_radii;         /* [n], or NULL */
+  float max_screen_radius;        /* > 0 with max_radii and GS_DENSIFY_PRUNE: drop larger unsplit originals */
 } gs_densify_args;
 size_t gs_densify_workspace_bytes(int32_t n);
 gs_status gs_densify_count(const gs_densify_args *a, gs_stream_t stream);

@@ -229,6 +229,14 @@ class GsDensifyArgs(C.Structure):
         ("adam_m_in", GsModelArrays), ("adam_v_in", GsModelArrays), ("workspace", _vp),
         ("workspace_bytes", C.c_size_t), ("counters", _vp), ("out", GsModelArrays),
         ("adam_m_out", GsModelArrays), ("adam_v_out", GsModelArrays),
+        ("grad_accum", _vp), ("grad_denom", _vp), ("max_radii", _vp), ("max_screen_radius", C.c_float),
+    ]
+
+
+class GsDensityStatsArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("image_width", C.c_int32), ("image_height", C.c_int32), ("vis", _vp), ("radii", _vp),
+        ("grad_sums", _vp), ("g_means2d", _vp), ("grad_accum", _vp), ("denom", _vp), ("max_radii", _vp),
     ]
 
 
@@ -240,7 +248,7 @@ EXPORTS = (
     "gs_project_backward_pose",
     "gs_blend_backward_groups", "gs_blend_backward_lane_stats", "gs_gather_partials", "gs_frame_workspace_bytes", "gs_tile_workspace_bytes", "gs_render_forward",
     "gs_render_backward", "gs_frame_offsets", "gs_tile_offsets", "gs_adam_step", "gs_project_backward_adam", "gs_loss_workspace_bytes", "gs_loss_forward", "gs_loss_backward",
-    "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit",
+    "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit", "gs_density_accumulate",
     "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
 )
 
@@ -302,13 +310,14 @@ def _declare(lib):
     lib.gs_densify_workspace_bytes.restype = C.c_size_t
     lib.gs_densify_count.argtypes = [P(GsDensifyArgs), _vp]
     lib.gs_densify_emit.argtypes = [P(GsDensifyArgs), _vp]
+    lib.gs_density_accumulate.argtypes = [P(GsDensityStatsArgs), _vp]
     lib.gs_blend_features_forward.argtypes = [P(GsFeatureFwdArgs), _vp]
     lib.gs_blend_features_backward.argtypes = [P(GsFeatureBwdArgs), _vp]
     lib.gs_gather_feature_partials.argtypes = [P(GsFeatureGatherArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
-              "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials"):
+              "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -53,6 +53,23 @@ class TrainingConfig:
     # after a densification the reference builds a fresh Adam (optimizer.py:133-137: moments and step
     # counts dropped); False keeps the kept Gaussians' moments (new ones start at zero)
     reset_adam_on_densify: bool = False
+    # what densification reads: "xyz_grad", |dL/dxyz| of the iteration's one view, or "screen", the
+    # 3DGS criterion: the NDC-unit gradient norm at the projected centre, averaged over the views that
+    # saw the Gaussian since the last densification (the quantity densify_grad_threshold is the 3DGS
+    # value of)
+    densify_criterion: str = "xyz_grad"
+    prune_screen_radius: float = 0.0   # "screen": also prune Gaussians whose largest screen radius (px) exceeded it; 0 = off
+    # cap opacities at 0.01 every this many iterations while densifying (0 = never); a Gaussian the
+    # training has not raised above min_opacity again by the next densification is pruned there
+    opacity_reset_interval: int = 0
+
+    def check(self) -> None:
+        """Values no run can use (the trainer asks at setup)."""
+        if self.densify_criterion not in DENSIFY_CRITERIA:
+            raise ValueError(f"densify_criterion must be one of {DENSIFY_CRITERIA}, got {self.densify_criterion!r}")
+
+
+DENSIFY_CRITERIA = ("xyz_grad", "screen")
 
 
 def _need_yaml():

@@ -8,6 +8,10 @@
 // bases (fixed order).  Emit: the same classification, block-local
 // exclusive scans and the bases give every output row its index; outputs are
 // grouped [kept | split - | split + | clones], index order within each.
+//
+// gs_density_accumulate (k_density_accumulate) keeps the screen-space
+// statistics the classification can read instead of |xyz_grad|: one streaming
+// launch after a rendered view's backward.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -35,9 +39,15 @@ __device__ Cls classify(const gs_densify_args &a, int i) {
   const bool prune = (a.flags & GS_DENSIFY_PRUNE) != 0;
   const bool alive = !prune || sigmoidf_(op) > a.min_opacity;  // optimizer.py:64
   bool split = false, clone = false;
-  if (a.xyz_grad) {
-    const float *g = a.xyz_grad + 3 * (size_t)i;
-    const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);  // .norm(dim=-1)
+  if (a.xyz_grad || a.grad_accum) {
+    float gn;
+    if (a.grad_accum) {  // mean screen-space gradient over the views that saw i
+      const float d = a.grad_denom[i];
+      gn = d > 0.f ? a.grad_accum[i] / d : 0.f;
+    } else {
+      const float *g = a.xyz_grad + 3 * (size_t)i;
+      gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);  // .norm(dim=-1)
+    }
     const bool hot = gn > a.grad_threshold;
     split = (a.flags & GS_DENSIFY_SPLIT) && hot && c.smean > a.split_size * a.scene_extent;   // :137
     clone = (a.flags & GS_DENSIFY_CLONE) && hot && c.smean < a.clone_size * a.scene_extent;   // :166
@@ -46,9 +56,11 @@ __device__ Cls classify(const gs_densify_args &a, int i) {
   const float o = sigmoidf_(op);
   c.child_op = fminf(fmaxf(logf(o / (1.f - o)), -6.f), 6.f);
   const bool child_alive = !prune || sigmoidf_(c.child_op) > a.min_opacity;
-  c.keep = !split && alive;
+  // an unsplit original larger on screen than max_screen_radius goes with the prune
+  const bool big = prune && a.max_radii && a.max_screen_radius > 0.f && a.max_radii[i] > a.max_screen_radius;
+  c.keep = !split && alive && !big;
   c.split = split && child_alive;
-  c.clone = clone && alive;
+  c.clone = clone && alive && !big;
   return c;
 }
 
@@ -228,6 +240,8 @@ inline unsigned nblocks(int n) { return (unsigned)((n + kB - 1) / kB); }
 gs_status check_args(const gs_densify_args *a, const char *what) {
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
   if (a->n < 0 || a->rest_floats < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad size", what);
+  if (a->grad_accum && (a->xyz_grad || !a->grad_denom))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: grad_accum needs grad_denom and excludes xyz_grad", what);
   if (a->n > 0 && (!a->in.xyz || !a->in.features_dc || !a->in.scaling || !a->in.rotation || !a->in.opacity ||
                    (a->rest_floats > 0 && !a->in.features_rest) || !a->counters || !a->workspace ||
                    a->workspace_bytes < gs_densify_workspace_bytes(a->n)))
@@ -235,10 +249,47 @@ gs_status check_args(const gs_densify_args *a, const char *what) {
   return GS_OK;
 }
 
+// One rendered view added to the density statistics (header, "Densification"):
+// 1 B (vis) per Gaussian; per visible one 8 B of its 40 B grad_sums row (the
+// row's cache lines move whole), 8 B g_means2d, 4 B radius, and the three
+// statistics read and written (24 B): ~70 B of traffic.
+__global__ __launch_bounds__(kB) void k_density_accumulate(gs_density_stats_args a, float sx, float sy) {
+  const int g = blockIdx.x * kB + threadIdx.x;
+  if (g >= a.n || !a.vis[g]) return;
+  float gx = 0.f, gy = 0.f;
+  if (a.grad_sums) {
+    const float2 s = *reinterpret_cast<const float2 *>(a.grad_sums + (size_t)g * GS_PAIR_GRAD_FLOATS);
+    gx = s.x;
+    gy = s.y;
+  }
+  if (a.g_means2d) {
+    const float2 m = reinterpret_cast<const float2 *>(a.g_means2d)[g];
+    gx += m.x;
+    gy += m.y;
+  }
+  const float nx = sx * gx, ny = sy * gy;
+  a.grad_accum[g] += sqrtf(nx * nx + ny * ny);
+  a.denom[g] += 1.f;
+  a.max_radii[g] = fmaxf(a.max_radii[g], a.radii[g]);
+}
+
 }  // namespace
 
 extern "C" size_t gs_densify_workspace_bytes(int32_t n) {
   return n > 0 ? sizeof(uint32_t) * 3 * (size_t)nblocks(n) : 0;
+}
+
+extern "C" gs_status gs_density_accumulate(const gs_density_stats_args *a, gs_stream_t stream) {
+  static const char *what = "gs_density_accumulate";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (a->n < 0 || a->image_width <= 0 || a->image_height <= 0)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad size (n >= 0, image_width and image_height > 0)", what);
+  if (a->n == 0) return GS_OK;
+  if (!a->vis || !a->radii || !a->grad_accum || !a->denom || !a->max_radii)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null vis, radii, grad_accum, denom or max_radii", what);
+  k_density_accumulate<<<nblocks(a->n), kB, 0, (hipStream_t)stream>>>(*a, 0.5f * (float)a->image_width,
+                                                                       0.5f * (float)a->image_height);
+  return gs_internal_check_launch(what);
 }
 
 extern "C" gs_status gs_densify_count(const gs_densify_args *a, gs_stream_t stream) {

@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
+from .rasterizer import DensityStats
 
 
 def build_rotation_matrix(q: torch.Tensor) -> torch.Tensor:
@@ -57,10 +58,20 @@ class GaussianModel(nn.Module):
         self.register_buffer("xyz_gradient_accum", torch.zeros(0, 3))
         self.register_buffer("denom", torch.zeros(0, 1))
         self.register_buffer("max_radii2D", torch.zeros(0))
+        # the statistics the renderer fills (render(..., density_stats=)) and the "screen"
+        # densification reads; zeros of the model's size wherever the three buffers above are re-made
+        self.density_stats = DensityStats(0, self._xyz.device)
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
         self.opacity_activation = torch.sigmoid
         self.rotation_activation = F.normalize
+
+    def _apply(self, fn, *args, **kwargs):
+        """Module.to / .cuda: the statistics follow the parameters (as zeros)."""
+        out = super()._apply(fn, *args, **kwargs)
+        if self.density_stats.device != self._xyz.device:
+            self.density_stats = DensityStats(self.get_num_points(), self._xyz.device)
+        return out
 
     def oneup_sh_degree(self) -> None:
         """Raise the rendered SH degree by one, up to max_sh_degree."""
@@ -75,10 +86,13 @@ class GaussianModel(nn.Module):
         self._scaling = nn.Parameter(scaling.contiguous())
         self._rotation = nn.Parameter(rot.contiguous())
         self._opacity = nn.Parameter(opacity.contiguous())
-        n, dev = xyz.shape[0], xyz.device
+        self._reset_stats(xyz.shape[0], xyz.device)
+
+    def _reset_stats(self, n: int, dev) -> None:
         self.xyz_gradient_accum = torch.zeros(n, 3, device=dev)
         self.denom = torch.zeros(n, 1, device=dev)
         self.max_radii2D = torch.zeros(n, device=dev)
+        self.density_stats = DensityStats(n, dev)
 
     @torch.no_grad()
     def create_from_random(self, num_points: int, scene_extent: float = 1.0,
@@ -190,15 +204,25 @@ class GaussianModel(nn.Module):
     def densify_and_prune(self, grad_threshold: float, scene_extent: float, min_opacity: float = 0.01,
                           optimizer: Optional[torch.optim.Optimizer] = None, seed: Optional[int] = None,
                           split: bool = True, clone: bool = True, prune: bool = True,
-                          xyz_grad: Optional[torch.Tensor] = None) -> dict:
+                          xyz_grad: Optional[torch.Tensor] = None, stats: Optional[DensityStats] = None,
+                          max_screen_radius: float = 0.0) -> dict:
         """Split large / clone small high-gradient Gaussians, then drop those
         with opacity <= min_opacity, in one GPU pass (semantics in
         include/gsplat_mi355x.h, "Densification").  With `optimizer`, its
         Adam moments follow the Gaussians (new ones start at zero) and its
-        parameter references are replaced.  Returns the output counts."""
+        parameter references are replaced.  Returns the output counts.
+        stats: a DensityStats of the model's size: the gradient test reads its
+        mean screen-space gradient instead of |xyz_grad| (not both), and, with
+        prune and max_screen_radius > 0, unsplit Gaussians whose max_radii
+        exceed it are dropped too."""
         params = self.parameter_list()
         n, dev = self.get_num_points(), self._xyz.device
-        grad = xyz_grad if xyz_grad is not None else self._xyz.grad
+        if stats is not None:
+            if xyz_grad is not None:
+                raise ValueError("densify_and_prune takes stats or xyz_grad, not both")
+            if stats.n != n or stats.device != dev:
+                raise ValueError(f"stats holds {stats.n} Gaussians on {stats.device}, the model {n} on {dev}")
+        grad = None if stats is not None else (xyz_grad if xyz_grad is not None else self._xyz.grad)
         for p in params:
             if not (p.is_cuda and p.is_contiguous()):
                 raise RuntimeError("densify needs contiguous parameters on a HIP device")
@@ -226,6 +250,9 @@ class GaussianModel(nn.Module):
         a.adam_m_in = arrays([st.get("exp_avg") for st in states])
         a.adam_v_in = arrays([st.get("exp_avg_sq") for st in states])
         a.workspace, a.workspace_bytes, a.counters = N.ptr(ws), ws.numel(), N.ptr(counters)
+        if stats is not None:
+            a.grad_accum, a.grad_denom = N.ptr(stats.grad_accum), N.ptr(stats.denom)
+            a.max_radii, a.max_screen_radius = N.ptr(stats.max_radii), float(max_screen_radius)
         stream = N.stream_ptr()
         N.check(lib.gs_densify_count(C.byref(a), stream), "gs_densify_count")
         kept, nsplit, ncl, n_out = (int(v) for v in counters.tolist())
@@ -253,9 +280,7 @@ class GaussianModel(nn.Module):
                     optimizer.state[q] = nst
         (self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
          self._opacity) = new
-        self.xyz_gradient_accum = torch.zeros(n_out, 3, device=dev)
-        self.denom = torch.zeros(n_out, 1, device=dev)
-        self.max_radii2D = torch.zeros(n_out, device=dev)
+        self._reset_stats(n_out, dev)
         return {"kept": kept, "split": nsplit, "cloned": ncl, "n": n_out}
 
     def density_and_split(self, grad_threshold: float, scene_extent: float) -> None:
@@ -271,7 +296,4 @@ class GaussianModel(nn.Module):
         """gaussian_model.py:181-197: keep the Gaussians where mask is True."""
         (self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
          self._opacity) = [nn.Parameter(p.data[mask].contiguous()) for p in self.parameter_list()]
-        n, dev = self.get_num_points(), self._xyz.device
-        self.xyz_gradient_accum = torch.zeros(n, 3, device=dev)
-        self.denom = torch.zeros(n, 1, device=dev)
-        self.max_radii2D = torch.zeros(n, device=dev)
+        self._reset_stats(self.get_num_points(), self._xyz.device)

@@ -58,6 +58,10 @@ class GraphedStep:
     `self.stream` (torch.cuda.stream(gstep.stream)) to keep everything on one
     queue; otherwise each step joins the current stream both ways.
 
+    Density-control statistics are out of scope here: a GraphedStep neither
+    accepts a DensityStats nor adds to the model's (its replayed backward has
+    no gs_density_accumulate node); gather them with GaussianRenderer.render.
+
     capacity / window: test knobs -- the tile workspace's capacity and the
     depth-key window (key_base, key_bits) of the next capture (default: the
     eager path's guesses, rasterizer._T_SEEN and rasterizer._window_for)."""

@@ -246,7 +246,13 @@ class DensityController:
     """optimizer.py:34-88: densify in [densify_from_iter, densify_until_iter]
     every densify_interval iterations; split / clone by |dL/dxyz| and prune
     opacity <= min_opacity in one GPU pass (GaussianModel.densify_and_prune),
-    the Adam state following the Gaussians."""
+    the Adam state following the Gaussians.  With config.densify_criterion
+    "screen" the gradient test reads the model's accumulated screen-space
+    statistics (gaussians.density_stats) and config.prune_screen_radius joins
+    the prune.  dist: the trainer's process group module when data parallel:
+    every rank has seen other views, so the statistics are all-reduced right
+    before (SUM of grad_accum and denom, MAX of max_radii) and every rank
+    takes the same decisions."""
 
     def __init__(self, config):
         self.config = config
@@ -256,10 +262,19 @@ class DensityController:
         return c.densify_from_iter <= iteration <= c.densify_until_iter and iteration % c.densify_interval == 0
 
     @torch.no_grad()
-    def densify_and_prune(self, gaussians, optimizer, iteration: int, scene_extent: float) -> dict:
-        return gaussians.densify_and_prune(self.config.densify_grad_threshold, scene_extent,
-                                           getattr(self.config, "min_opacity", 0.01), optimizer=optimizer,
-                                           seed=0x5EED0000 + iteration)
+    def densify_and_prune(self, gaussians, optimizer, iteration: int, scene_extent: float, dist=None) -> dict:
+        c = self.config
+        kw = {}
+        if getattr(c, "densify_criterion", "xyz_grad") == "screen":
+            stats = gaussians.density_stats
+            if dist is not None and stats.n:
+                dist.all_reduce(stats.grad_accum, op=dist.ReduceOp.SUM)
+                dist.all_reduce(stats.denom, op=dist.ReduceOp.SUM)
+                dist.all_reduce(stats.max_radii, op=dist.ReduceOp.MAX)
+            kw = {"stats": stats, "max_screen_radius": float(getattr(c, "prune_screen_radius", 0.0))}
+        return gaussians.densify_and_prune(c.densify_grad_threshold, scene_extent,
+                                           getattr(c, "min_opacity", 0.01), optimizer=optimizer,
+                                           seed=0x5EED0000 + iteration, **kw)
 
 
 class GaussianOptimizer:
@@ -302,9 +317,10 @@ class GaussianOptimizer:
         pg[3]["lr"] = base * (c.scaling_lr / c.position_lr_init)
         pg[4]["lr"] = base * (c.rotation_lr / c.position_lr_init)
 
-    def densify_and_prune(self, iteration: int, scene_extent: float):
+    def densify_and_prune(self, iteration: int, scene_extent: float, dist=None):
         if self.density_controller.should_densify(iteration):
-            info = self.density_controller.densify_and_prune(self.gaussians, self.optimizer, iteration, scene_extent)
+            info = self.density_controller.densify_and_prune(self.gaussians, self.optimizer, iteration, scene_extent,
+                                                             dist=dist)
             if getattr(self.config, "reset_adam_on_densify", False):
                 self.setup_optimizer()
             return info
@@ -312,3 +328,18 @@ class GaussianOptimizer:
 
     def reset_opacity(self) -> None:
         self.gaussians.reset_opacity()
+
+    @torch.no_grad()
+    def cap_opacity(self, max_opacity: float = 0.01) -> None:
+        """The 3DGS opacity reset: every opacity above max_opacity comes down to
+        it -- _opacity.data = minimum(_opacity, logit(max_opacity)), the logit
+        rounded to fp32 once -- and the opacity parameter's Adam moments start
+        over from zero (its step count stays; no other state is touched).
+        reset_opacity keeps the reference's own semantics (every opacity set)."""
+        p = self.gaussians._opacity
+        cap = torch.tensor(math.log(max_opacity / (1.0 - max_opacity)), dtype=torch.float32, device=p.device)
+        torch.minimum(p.data, cap, out=p.data)  # (in place: the address other launches hold stays)
+        st = self.optimizer.state.get(p) if self.optimizer is not None else None
+        if st:
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()

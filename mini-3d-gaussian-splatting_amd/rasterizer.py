@@ -7,7 +7,8 @@ One `render` = the reference's four stages (renderer.py:31-114):
   gs_radix_sort_pairs  stable sort of the entries by tile id
   gs_tile_ranges       per-tile lists
   gs_blend_forward     per-pixel compositing        (:273-367)
-and the backward: gs_blend_backward + gs_project_backward.
+and the backward: gs_blend_backward + gs_project_backward, then, when the
+render was given a DensityStats, one gs_density_accumulate.
 
 All buffers are torch tensors from the caching allocator; the HIP library
 never allocates.  One host synchronisation per forward reads the visible
@@ -269,6 +270,62 @@ def _check_inputs(xyz: torch.Tensor):
     if not xyz.is_cuda:
         raise RuntimeError("the MI355X renderer needs Gaussians on a HIP device (got %s); "
                            "there is no CPU path" % xyz.device)
+
+
+class DensityStats:
+    """The 3DGS density-control statistics of `n` Gaussians on `device`, three
+    contiguous fp32 [n] tensors: grad_accum (sum over the views that saw a
+    Gaussian of the NDC-unit norm of dL/d(its projected centre)), denom (how
+    many views saw it) and max_radii (its largest screen radius in them).
+
+    render(..., density_stats=stats) / rasterize(..., density_stats=stats)
+    add that view to them at the end of its backward (gs_density_accumulate,
+    on the backward's stream).  No backward, no statistics: a forward under
+    torch.no_grad(), or one whose backward never runs, adds nothing; a second
+    backward of the same frame (retain_graph) adds the view a second time."""
+    __slots__ = ("n", "grad_accum", "denom", "max_radii")
+
+    def __init__(self, n: int, device):
+        self.n = int(n)
+        self.grad_accum, self.denom, self.max_radii = (
+            torch.zeros((self.n,), dtype=torch.float32, device=device) for _ in range(3))
+
+    @property
+    def device(self) -> torch.device:
+        return self.grad_accum.device
+
+    def reset(self) -> None:
+        for t in (self.grad_accum, self.denom, self.max_radii):
+            t.zero_()
+
+    def mean_grad(self) -> torch.Tensor:
+        """grad_accum / denom, 0 where no view saw the Gaussian."""
+        seen = self.denom > 0
+        return torch.where(seen, self.grad_accum / self.denom.clamp_min(1.0), torch.zeros_like(self.grad_accum))
+
+
+def _check_density_stats(stats, n: int, dev) -> None:
+    if not isinstance(stats, DensityStats):
+        raise TypeError(f"density_stats must be a DensityStats, got {type(stats).__name__}")
+    if stats.n != n:
+        raise ValueError(f"density_stats holds {stats.n} Gaussians, the render {n}")
+    for name in ("grad_accum", "denom", "max_radii"):
+        t = getattr(stats, name)
+        if tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"density_stats.{name} must be a contiguous fp32 [{n}] tensor on {dev}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _accumulate_density(lib, cam: CameraParams, stats, n: int, vis, radii, grad_sums, g_means2d, s) -> None:
+    """One gs_density_accumulate: this view added to `stats` (the last launch
+    of its backward).  grad_sums: the address of the [n, 10] sums the
+    projection backward read, or None for a frame without a blend gradient."""
+    if stats is None or n == 0:
+        return
+    a = N.GsDensityStatsArgs(n, int(cam.image_width), int(cam.image_height), N.ptr(vis), N.ptr(radii),
+                             grad_sums, N.ptr(g_means2d), N.ptr(stats.grad_accum), N.ptr(stats.denom),
+                             N.ptr(stats.max_radii))
+    N.check(lib.gs_density_accumulate(C.byref(a), s), "gs_density_accumulate")
 
 
 class _Frame:
@@ -831,8 +888,10 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
 def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotation, logits, opacity,
                       means2d, conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit=False,
-                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None, feat=None):
-    """outputs: the forward's (image, alpha, depth), unmodified -- with the
+                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None, feat=None, density=None):
+    """density: optional (DensityStats, the forward's radii): the view is added
+    to the statistics after the projection backward's last row range.
+    outputs: the forward's (image, alpha, depth), unmodified -- with the
     frame's clamp flags they are the blend backward's per-pixel state.
     feat: optional _FeaturePass with a cotangent on the feature image (a
     stage-path frame): its chunks' geometry sums are added to the colour
@@ -850,7 +909,7 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     if isinstance(fr, _FastFrame):
         return _backward_frame(cam, fr, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics, g_image,
                                g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
-                               outputs, d_view)
+                               outputs, d_view, density)
     lib = N.load()
     dev = xyz.device
     n = int(xyz.shape[0])
@@ -921,6 +980,8 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                             N.ptr(slot_live), N.ptr(grad_sums), fr.groups)
     StageTimer.mark("project_bwd")
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
+    if density is not None:
+        _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], N.ptr(grad_sums) or None, gm, s)
     StageTimer.mark("~end_bwd")
     return grads
 
@@ -1004,7 +1065,7 @@ def _blend_outputs(outputs):
 
 def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rotation, logits, opacity, means2d,
                     conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
-                    outputs, d_view=None):
+                    outputs, d_view=None, density=None):
     """backward_pipeline through gs_render_backward (the frame of
     _forward_frame): the blend backward and the gather in the library, then
     the projection backward -- there too unless the data-parallel reduction
@@ -1042,9 +1103,13 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     if ev is not None:
         ba.blend_events[0], ba.blend_events[1] = ev[0].handle, ev[1].handle
     N.check(lib.gs_render_backward(C.byref(ba), s), "gs_render_backward")
+    # (the gathered sums in the frame workspace, when this backward had a blend gradient)
+    sums = ba.grad_sums if pair_grads is not None else None
     if ba.project:
         if rows_ready is not None:
             rows_ready(0, n)
+        if density is not None:
+            _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], sums, gm, s)
         return grads
     # the projection backward from here: per row range, each range's
     # reduction issued as soon as its rows are queued, or with the pose gradient
@@ -1053,8 +1118,10 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     pb = N.GsProjectBwdArgs(fa.cam, ba.g, N.ptr(means2d), N.ptr(conics), fa.vis, fws + fo[1], fws + fo[8], None,
                             None, N.ptr(gm),
                             N.ptr(gc), N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col),
-                            N.ptr(d_op), N.ptr(d_sh), None, ba.grad_sums if pair_grads is not None else None, 0)
+                            N.ptr(d_op), N.ptr(d_sh), None, sums, 0)
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
+    if density is not None:
+        _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], sums, gm, s)
     return grads
 
 
@@ -1193,10 +1260,11 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None):
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=True)
+        ctx.density = None if density_stats is None else (density_stats, radii)
         n, channels = int(features.shape[0]), int(features.shape[1])
         staged = _stage_features(features)
         feat_image = _feature_forward(cam, fr, staged, channels, n, xyz.device)
@@ -1224,7 +1292,8 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
         d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
-            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, feat=feat)
+            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, feat=feat,
+            density=ctx.density)
         need = ctx.needs_input_grad
         d_features = None
         if need[7] and feat is not None:
@@ -1243,7 +1312,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                d_features, None, None, None, None, g_view)
+                d_features, None, None, None, None, g_view, None)
 
 
 class RasterizeGaussians(torch.autograd.Function):
@@ -1252,7 +1321,9 @@ class RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None):
+        # density_stats: a DensityStats this frame's backward adds the view to (it needs the
+        # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape)
         # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
         # Gaussians' device, given only to receive its gradient -- the forward
         # reads the pose from `cam`, whose values are the same
@@ -1261,6 +1332,7 @@ class RasterizeGaussians(torch.autograd.Function):
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]))
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
+        ctx.density = None if density_stats is None else (density_stats, radii)
         ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[11] else None
         # (the outputs image / alpha / depth too: the blend backward's per-pixel
         # state; autograd refuses the backward if they were modified in place)
@@ -1281,7 +1353,7 @@ class RasterizeGaussians(torch.autograd.Function):
         d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, None if g_alpha is None else g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
-            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view)
+            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, density=ctx.density)
         need = ctx.needs_input_grad
         g_view = None
         if d_view is not None:
@@ -1295,12 +1367,16 @@ class RasterizeGaussians(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                None, None, None, None, g_view)
+                None, None, None, None, g_view, None)
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
-              sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None):
-    """features: optional floating-point [N, C] tensor on the Gaussians' device,
+              sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None, density_stats=None):
+    """density_stats: optional DensityStats of N Gaussians on their device: the
+    backward of this render ends with one gs_density_accumulate that adds the
+    view to it (checked here, before any launch; see DensityStats for what a
+    missing or repeated backward means).  Without it the launches are the same.
+    features: optional floating-point [N, C] tensor on the Gaussians' device,
     C in 1..GS_MAX_FEATURE_CHANNELS: an eighth output follows the seven, the
     feature image [C, H, W] fp32 = sum_i c_i features[g_i] per pixel with the
     colour pass's own weights c_i (no background, clamp or normalisation);
@@ -1336,6 +1412,8 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
             raise ValueError(f"{name} must hold {list(tail)} per Gaussian for N = {n}, got {tuple(t.shape)}")
         return t if t.dtype == torch.float32 else t.float()
 
+    if density_stats is not None:
+        _check_density_stats(density_stats, n, xyz.device)
     xyz = prep("xyz", xyz, (3,))
     cov3d = prep("cov3d", cov3d, (3, 3))
     scaling = prep("scaling", scaling, (3,))
@@ -1374,12 +1452,16 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     xyz, _ = _rows(xyz, 3)
     logits, _ = _rows(logits, 3)
     opacity, _ = _rows(opacity, 1)
+    # (the statistics ride behind `view`, only when given: without them the calls are the ones they were)
+    stats = () if density_stats is None else (density_stats,)
     if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
+        if stats:
+            stats = (None,) + stats
         if features is not None:
             return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
-                                                   cam, bool(opacity_is_logit), sh_degree, grad_dest)
+                                                   cam, bool(opacity_is_logit), sh_degree, grad_dest, *stats)
         return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                        bool(opacity_is_logit), sh_degree, grad_dest)
+                                        bool(opacity_is_logit), sh_degree, grad_dest, *stats)
     if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
         raise ValueError(f"view must be a floating-point [3,4] or [4,4] tensor, got {view.dtype} {tuple(view.shape)}")
     # (differentiable, as the reference's .to(device): the gradient returns to
@@ -1387,6 +1469,6 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     view = view.to(device=xyz.device, dtype=torch.float32)
     if features is not None:
         return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
-                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, view)
+                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, view, *stats)
     return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                    bool(opacity_is_logit), sh_degree, grad_dest, view)
+                                    bool(opacity_is_logit), sh_degree, grad_dest, view, *stats)

@@ -26,6 +26,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     reference.
   * `render(..., features=F)` (not in the reference) also returns
     "features": F [N, C] composited with the colour pass's own weights.
+  * `render(..., density_stats=S)` (not in the reference) adds the view to the
+    density-control statistics S at the end of its backward (DensityStats).
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
     switches on view-dependent SH colour; at 0 -- the default for the
     reference's own model and stubs -- colours are the reference's
@@ -40,7 +42,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _native as N
-from .rasterizer import CameraParams, rasterize
+from .rasterizer import CameraParams, DensityStats, rasterize
 
 
 @dataclass
@@ -129,8 +131,20 @@ class GaussianRenderer:
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
     def render(self, camera, gaussians, settings: RenderSettings,
-               features: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        """features: optional floating-point [N, C] per-Gaussian values
+               features: Optional[torch.Tensor] = None,
+               density_stats: Optional[DensityStats] = None) -> Dict[str, torch.Tensor]:
+        """density_stats: optional DensityStats of the model's size on its
+        device.  The backward of this render then ends with one launch that
+        adds the view to them: per visible Gaussian the NDC-unit norm of
+        dL/d(viewspace_points) -- the blend's part, which never surfaces as a
+        .grad, plus the caller's own cotangent on out["viewspace_points"] --
+        one more view seen, and the largest radius (what 3DGS trainers gather
+        with viewspace_points.retain_grad() + add_densification_stats).  No
+        backward, no statistics: a render under torch.no_grad(), or one whose
+        backward never runs, adds nothing; backward twice (retain_graph) adds
+        the view twice.  A size, device, dtype or layout mismatch is a
+        ValueError before anything is launched.
+        features: optional floating-point [N, C] per-Gaussian values
         (normals, embeddings, positions, ...) on the Gaussians' device.  The
         result then also holds "features" [C, H, W] fp32: each pixel's
         sum_i c_i features[g_i] with exactly the weights c_i the colour pass
@@ -196,6 +210,8 @@ class GaussianRenderer:
         extra = dict(pose)
         if features is not None:
             extra["features"] = features
+        if density_stats is not None:
+            extra["density_stats"] = density_stats
         image, alpha, depth, means2d, conics, radii, vis, *feature_image = rasterize(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
             sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **extra)

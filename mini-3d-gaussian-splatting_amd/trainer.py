@@ -5,7 +5,11 @@ One iteration: pick a training camera, render it (HIP path), fused L1 +
 D-SSIM against its image, backward, [N > 1: one RCCL mean all-reduce of the
 Gaussian gradients], learning-rate schedule, FusedAdam step, and density
 control every densify_interval iterations inside [densify_from_iter,
-densify_until_iter] (optimizer.py:34-141).  Nothing in a step reads a value
+densify_until_iter] (optimizer.py:34-141) -- on |dL/dxyz| of the iteration's
+view, or with densify_criterion = "screen" on the 3DGS statistics every
+render's backward adds to gaussians.density_stats (then also
+prune_screen_radius and, every opacity_reset_interval iterations, the 3DGS
+opacity reset).  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.
 
 Data parallel: with torch.distributed initialised,
@@ -45,6 +49,7 @@ class GaussianTrainer:
         self._reducer = None
         self._reducer_n = -1
         self._perm: Optional[np.ndarray] = None
+        self.last_densify: Optional[dict] = None  # the counts of the latest densification
 
     # -- setup (trainer.py:32-44) ------------------------------------------
     def _device(self) -> torch.device:
@@ -56,6 +61,7 @@ class GaussianTrainer:
         the camera order -- shared by setup() and load_checkpoint() (a resumed
         run needs them as much as a fresh one)."""
         c = self.config
+        c.check()
         if self.dataset is None:
             self.dataset = load_dataset(c.data_path, device=self._device())
         if torch.distributed.is_available() and torch.distributed.is_initialized() and \
@@ -67,6 +73,7 @@ class GaussianTrainer:
 
     def setup(self) -> None:
         c = self.config
+        c.check()
         dev = self._device()
         self._setup_run()
         g = GaussianModel(c)
@@ -112,7 +119,10 @@ class GaussianTrainer:
                 self._reducer = GradAllReduce(params, self._dist).attach(g)
                 self._reducer_n = g.get_num_points()
             self._reducer.params = params
-        out = self.renderer.render(camera, g, self._settings(camera))
+        if c.densify_criterion == "screen":
+            out = self.renderer.render(camera, g, self._settings(camera), density_stats=g.density_stats)
+        else:
+            out = self.renderer.render(camera, g, self._settings(camera))
         target = camera._image
         total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
         total.backward()
@@ -123,9 +133,13 @@ class GaussianTrainer:
             self._reducer.reduce_and_step(opt.optimizer)
         else:
             opt.step()
-        info = opt.densify_and_prune(self.iteration, self.scene_extent)
+        info = opt.densify_and_prune(self.iteration, self.scene_extent, dist=self._dist)
         if info is not None:
             self._reducer = None
+            self.last_densify = info
+        if (c.opacity_reset_interval > 0 and self.iteration % c.opacity_reset_interval == 0
+                and self.iteration <= c.densify_until_iter):
+            opt.cap_opacity()
         return {"loss": total.detach(), "l1": l1, "dssim": dssim}
 
     def close(self) -> None:

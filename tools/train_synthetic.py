@@ -2,7 +2,8 @@
 offline): a Blender-format scene whose ground truth is rendered from a known
 Gaussian set at 800x800, then the full GaussianTrainer loop from a random
 init.  Prints one JSON line: iterations/s, test PSNR, Gaussian count.
-    python tools/train_synthetic.py [--iters 7000] [--views 100] [--size 800]"""
+    python tools/train_synthetic.py [--iters 7000] [--views 100] [--size 800]
+        [--criterion xyz_grad|screen] [--prune-screen-radius PX] [--opacity-reset-interval K]"""
 import argparse
 import json
 import math
@@ -59,9 +60,11 @@ def build_scene(pkg, views=100, size=800, gt_gaussians=200_000, device=None):
     return ds
 
 
-def make_trainer(pkg, ds, iters=7000):
+def make_trainer(pkg, ds, iters=7000, **density):
+    """density: TrainingConfig's densify_criterion / prune_screen_radius / opacity_reset_interval."""
     cfg = pkg.TrainingConfig(iterations=iters, num_random_points=100_000, log_interval=500,
-                             densify_until_iter=min(15000, iters // 2), output_path=os.path.join(ds.root, "out"))
+                             densify_until_iter=min(15000, iters // 2), output_path=os.path.join(ds.root, "out"),
+                             **density)
     tr = pkg.GaussianTrainer(cfg, ds)
     tr.setup()
     return tr
@@ -73,6 +76,9 @@ def main():
     ap.add_argument("--views", type=int, default=100)
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--gt-gaussians", type=int, default=200_000)
+    ap.add_argument("--criterion", default="xyz_grad", help="TrainingConfig.densify_criterion")
+    ap.add_argument("--prune-screen-radius", type=float, default=0.0)
+    ap.add_argument("--opacity-reset-interval", type=int, default=0)
     ap.add_argument("--profile-iters", type=int, default=0,
                     help="host profile (cProfile) of this many iterations after 100 warm ones, then exit")
     a = ap.parse_args()
@@ -80,7 +86,8 @@ def main():
     pkg = ge.load_package()
     ds = build_scene(pkg, a.views, a.size, a.gt_gaussians)
     n = a.gt_gaussians
-    tr = make_trainer(pkg, ds, a.iters)
+    tr = make_trainer(pkg, ds, a.iters, densify_criterion=a.criterion, prune_screen_radius=a.prune_screen_radius,
+                      opacity_reset_interval=a.opacity_reset_interval)
     if a.profile_iters:
         import cProfile
         import pstats
@@ -105,7 +112,7 @@ def main():
     v = tr.validate()
     print(json.dumps({"workload": f"C4 stand-in: synthetic Blender-format scene, {a.views} views {a.size}x{a.size}, "
                                   f"GT {n} Gaussians, random init 100k", "iterations": a.iters,
-                      "it_per_s": round(a.iters / dt, 1), "train_s": round(dt, 2), "psnr_init": round(p0, 2),
+                      "criterion": a.criterion, "it_per_s": round(a.iters / dt, 1), "train_s": round(dt, 2), "psnr_init": round(p0, 2),
                       "psnr_test": round(v["psnr"], 2), "gaussians": v["num_gaussians"],
                       "losses": [round(x, 4) for x in tr.train_losses]}), flush=True)
 
