@@ -123,12 +123,35 @@ typedef struct gs_gaussians {
   int64_t sh_rest_stride;
 } gs_gaussians;
 
+/* Screen-space low-pass filter (anti-aliasing; not in the reference).  With
+ * V0 = J cov_cam J^T + 1e-6 I (renderer.py:182-183), the projection works on
+ *   V = V0 + variance I
+ * wherever it read cov2d: the conic Q = inv(V) (the full 2x2 inverse), lmax,
+ * the radius and its clamp, the cull test, the tile rectangle, the depth key.
+ * With compensate != 0 the opacity written to the splat record is
+ *   opacity rho,  rho = sqrt(max(det V0 / det V, 2.5e-5))
+ * (after get_opacity's sigmoid when opacity_is_logit; determinants in double
+ * from the fp32 entries; the floor is Mip-Splatting's), so that a splat keeps
+ * its energy; nothing else reads rho.  variance: px^2, >= 0 and finite
+ * (0.3: 3DGS's dilation, 0.1: Mip-Splatting's); 0 is off whatever compensate
+ * says -- all zero is the unfiltered projection, bit for bit.  The blend, the
+ * feature replay, the gather and the density statistics read the record and
+ * the outputs: they do not know of the filter. */
+typedef struct gs_screen_filter {
+  float variance;
+  int32_t compensate;
+} gs_screen_filter;
+
 /* ---- Stage 1: _project_gaussians_3d_to_2d + _frustum_culling ----------
  * Replaces renderer.py:117-200 and :201-220.  One thread per Gaussian.
  * Writes the render() outputs means2d (viewspace_points), conics, radii and
  * visibility_filter, plus the splat record, tile rectangle and depth sort
  * key used by the later stages.  No atomics, no counters: the visible
- * count is produced by gs_bin_count. */
+ * count is produced by gs_bin_count.
+ * filter (gs_screen_filter): cov2d = V0 + variance I for the conic, the
+ * radius, the cull test, the rectangle and the key, and the record's opacity
+ * times rho when compensating.  A negative or non-finite variance:
+ * GS_ERR_INVALID_ARG before any HIP call. */
 typedef struct gs_project_args {
   gs_camera cam;
   gs_gaussians g;
@@ -152,6 +175,7 @@ typedef struct gs_project_args {
   int32_t key_bits;     /* 1..32 */
   uint32_t *key_minmax; /* [2 * ceil(n / 256)] per-block min / max of the visible bits(Z), for
                            gs_bin_count's counters[2..3] */
+  gs_screen_filter filter; /* all zero: none */
 } gs_project_args;
 gs_status gs_project_forward(const gs_project_args *a, gs_stream_t stream);
 
@@ -479,7 +503,17 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
  * Xc = Rv Xw + Tv (autograd of renderer.py:117-200), and, on the raw path,
  * through Sigma(exp(s), normalize(q)) (gaussian_model.py:200-207), and with
  * sh_degree > 0 through the SH colour into sh_rest and (via the view
- * direction) into xyz. */
+ * direction) into xyz.
+ * filter: the forward's gs_screen_filter.  inv(cov2d) is inv(V0 + variance I)
+ * (the raw path's double conic is rebuilt from it).  When compensating, with
+ * acc[5] the blend's gradient at the record opacity:
+ *   d_opacity = acc[5] rho (then the sigmoid chain),  d_rho = acc[5] opacity,
+ * and, where the floor does not bind (r = det V0 / det V > 2.5e-5),
+ *   d_V0 += d_rho / (2 rho) (adj(V0)^T / det V - r adj(V)^T / det V)
+ * entry by entry (V[0][1] and V[1][0] are separate) before the chain into J
+ * and cov_cam; where it binds rho is a constant.  A Gaussian whose only
+ * cotangent is on opacity then has geometry gradients.  A negative or
+ * non-finite variance: GS_ERR_INVALID_ARG before any HIP call. */
 typedef struct gs_project_bwd_args {
   gs_camera cam;
   gs_gaussians g;
@@ -506,6 +540,7 @@ typedef struct gs_project_bwd_args {
   float *grad_sums;            /* [n, GS_PAIR_GRAD_FLOATS]: g's partials summed (written first when
                                   pair_grads is given, else read as is); NULL: no blend gradient */
   int32_t partial_groups;      /* G of pair_grads / slot_live: the blend backward's cell_count */
+  gs_screen_filter filter;     /* the forward's; all zero: none */
 } gs_project_bwd_args;
 gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream);
 /* The gather alone: grad_sums[g] = (accumulate ? grad_sums[g] : 0) + the sum
@@ -769,6 +804,7 @@ typedef struct gs_render_fwd_args {
   int32_t M, T;
   uint32_t depth_min_bits, depth_max_bits; /* counters[2..3] */
   int32_t depth_alt, tile_alt;
+  gs_screen_filter filter;         /* (input) passed to gs_project_forward; all zero: none */
 } gs_render_fwd_args;
 /* GS_OK; M == 0: nothing drawn (renderer.py:74-83's background image is the
  * caller's); GS_NEED_CAPACITY / GS_RETRY_FULL_KEYS: see gs_status. */
@@ -796,6 +832,7 @@ typedef struct gs_render_bwd_args {
                                       capacity * flag_groups partials (a failed frame gathers zero slots) */
   const gs_adam_args *fused_adam;  /* with project = 1: gs_project_backward_adam with these tensors (no
                                       d_* written), or NULL: the plain projection backward */
+  gs_screen_filter filter;         /* the forward's, passed to the projection backward */
 } gs_render_bwd_args;
 gs_status gs_render_backward(gs_render_bwd_args *a, gs_stream_t stream);
 /* Byte offsets of the buffers inside the two workspaces (for diagnostics and

@@ -55,11 +55,16 @@ class GsGaussians(C.Structure):
     ]
 
 
+class GsScreenFilter(C.Structure):
+    """gs_screen_filter: variance (px^2, 0 = off) and the opacity compensation flag."""
+    _fields_ = [("variance", C.c_float), ("compensate", C.c_int32)]
+
+
 class GsProjectArgs(C.Structure):
     _fields_ = [
         ("cam", GsCamera), ("g", GsGaussians), ("means2d", _vp), ("conics", _vp), ("radii", _vp),
         ("vis", _vp), ("records", _vp), ("rects", _vp), ("depth_keys", _vp),
-        ("key_base", C.c_uint32), ("key_bits", C.c_int32), ("key_minmax", _vp),
+        ("key_base", C.c_uint32), ("key_bits", C.c_int32), ("key_minmax", _vp), ("filter", GsScreenFilter),
     ]
 
 
@@ -107,7 +112,7 @@ class GsProjectBwdArgs(C.Structure):
         ("rects", _vp), ("pair_offset", _vp), ("order", _vp), ("pair_grads", _vp), ("g_means2d", _vp),
         ("g_conics", _vp), ("d_xyz", _vp), ("d_cov3d", _vp), ("d_scaling", _vp),
         ("d_rotation", _vp), ("d_color_logits", _vp), ("d_opacity", _vp), ("d_sh_rest", _vp),
-        ("slot_live", _vp), ("grad_sums", _vp), ("partial_groups", C.c_int32),
+        ("slot_live", _vp), ("grad_sums", _vp), ("partial_groups", C.c_int32), ("filter", GsScreenFilter),
     ]
 
 
@@ -167,7 +172,7 @@ class GsRenderFwdArgs(C.Structure):
         ("pix_neval", _vp), ("resume", C.c_int32), ("poll_timeout_ms", C.c_int32), ("device_counts", C.c_int32),
         ("step_flags", _vp), ("frame_seq", _vp), ("M", C.c_int32), ("T", C.c_int32),
         ("depth_min_bits", C.c_uint32), ("depth_max_bits", C.c_uint32), ("depth_alt", C.c_int32),
-        ("tile_alt", C.c_int32),
+        ("tile_alt", C.c_int32), ("filter", GsScreenFilter),
     ]
 
 
@@ -179,6 +184,7 @@ class GsRenderBwdArgs(C.Structure):
         ("flags_zeroed", C.c_int32), ("project", C.c_int32), ("d_xyz", _vp), ("d_cov3d", _vp),
         ("d_scaling", _vp), ("d_rotation", _vp), ("d_color_logits", _vp), ("d_opacity", _vp), ("d_sh_rest", _vp),
         ("grad_sums", _vp), ("blend_events", _vp * 2), ("device_counts", C.c_int32), ("fused_adam", _vp),
+        ("filter", GsScreenFilter),
     ]
 
 

@@ -62,11 +62,19 @@ class TrainingConfig:
     # cap opacities at 0.01 every this many iterations while densifying (0 = never); a Gaussian the
     # training has not raised above min_opacity again by the next densification is pruned there
     opacity_reset_interval: int = 0
+    # screen-space low-pass filter of every render, training and evaluation (RenderSettings.screen_filter:
+    # the variance in px^2, 0 = off, 0.3 = 3DGS's dilation, 0.1 = Mip-Splatting's), and whether the
+    # opacities are scaled so that a filtered splat keeps its energy
+    screen_filter: float = 0.0
+    filter_compensate: bool = True
 
     def check(self) -> None:
         """Values no run can use (the trainer asks at setup)."""
         if self.densify_criterion not in DENSIFY_CRITERIA:
             raise ValueError(f"densify_criterion must be one of {DENSIFY_CRITERIA}, got {self.densify_criterion!r}")
+        s = float(self.screen_filter)
+        if not (s >= 0.0 and s != float("inf")):
+            raise ValueError(f"screen_filter must be a finite variance >= 0 (px^2), got {self.screen_filter!r}")
 
 
 DENSIFY_CRITERIA = ("xyz_grad", "screen")

@@ -143,7 +143,11 @@ __device__ __forceinline__ void color_logits(const gs_gaussians &G, const gs_cam
 // kHot: raw scale/rotation and DC colour (training); every input load is
 // issued at the top (under the visibility branch they were waited for in
 // further round trips).
-template <bool kHot>
+// kFilter (gs_screen_filter, variance > 0): cov2d = V0 + variance I from here
+// on, and with compensate the record's opacity times
+// rho = sqrt(max(det V0 / det V, kRhoFloor)), the determinants in double.
+constexpr double kRhoFloor = 2.5e-5;
+template <bool kHot, bool kFilter = false>
 __global__ __launch_bounds__(kBlock) void k_project_fwd(gs_project_args a) {
   __shared__ uint32_t s_mm[2][kBlock / kWave];
   const int g = blockIdx.x * kBlock + threadIdx.x;
@@ -210,6 +214,12 @@ __global__ __launch_bounds__(kBlock) void k_project_fwd(gs_project_args a) {
         V[i * 2 + j] = (JC[i * 3] * J[j * 3] + JC[i * 3 + 1] * J[j * 3 + 1]) + JC[i * 3 + 2] * J[j * 3 + 2];
     V[0] += 1e-6f;  // :182-183
     V[3] += 1e-6f;
+    [[maybe_unused]] double det0 = 0.0;
+    if constexpr (kFilter) {
+      det0 = (double)V[0] * (double)V[3] - (double)V[1] * (double)V[2];
+      V[0] += a.filter.variance;
+      V[3] += a.filter.variance;
+    }
     // conic = inv(cov2d) (:186) and lambda_max (:188) in double: LAPACK-grade
     const double va = V[0], vb = V[1], vc = V[2], vd = V[3];
     const double det = va * vd - vb * vc;
@@ -251,6 +261,9 @@ __global__ __launch_bounds__(kBlock) void k_project_fwd(gs_project_args a) {
       }
       float op = kHot ? op_pre : a.g.opacity[(int64_t)g * a.g.opacity_stride];
       if (a.g.opacity_is_logit) op = 1.f / (1.f + expf(-op));  // get_opacity
+      if constexpr (kFilter) {
+        if (a.filter.compensate) op *= (float)sqrt(fmax(det0 / det, kRhoFloor));
+      }
       float4 *rec = reinterpret_cast<float4 *>(a.records) + 3 * (int64_t)g;
       // record: mx my q00 q11 | qo o r g | b z off rinfo -- (q00, q11) adjacent so
       // that the blend's dx^2 q00, dy^2 q11 are one packed multiply
@@ -525,7 +538,10 @@ struct AdamOut {
 // through this function only, so the caller's barrier is reached.
 constexpr int kPoseVals = 15;
 constexpr int kPoseRow = 16;  // doubles per row of the partial buffer
-template <bool kHot, bool kPose = false, typename Sums, typename Out>
+// kFilter (gs_screen_filter, variance > 0): V = V0 + variance I, and when
+// compensating the opacity's gradient is scaled by rho and d_rho = acc[5]
+// opacity enters dV (header: Backward of the projection).
+template <bool kHot, bool kPose = false, bool kFilter = false, typename Sums, typename Out>
 __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, int g, Sums sums, Out &out,
                                                 double *pose = nullptr) {
   float scl_pre[3] = {0.f, 0.f, 0.f}, rot_pre[4] = {0.f, 0.f, 0.f, 0.f}, op_pre = 0.f;
@@ -590,13 +606,22 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
     }
   }
   float dop = acc[5];
+  // compensating: d_opacity = acc[5] rho, written once rho is formed (below);
+  // a zero acc[5] is written here as before
+  const bool comp = kFilter && a.filter.compensate != 0 && acc[5] != 0.f;
+  [[maybe_unused]] float op_val = 0.f, op_chain = 1.f;  // the record's opacity before rho; d opacity / d input
+  if constexpr (kFilter) op_val = kHot ? op_pre : a.g.opacity[(int64_t)g * a.g.opacity_stride];
   if (a.g.opacity_is_logit) {  // through get_opacity's sigmoid, as torch's sigmoid_backward
     const float o = 1.f / (1.f + expf(-(kHot ? op_pre : a.g.opacity[(int64_t)g * a.g.opacity_stride])));
     dop = (dop * (1.f - o)) * o;
+    if constexpr (kFilter) {
+      op_val = o;
+      op_chain = (1.f - o) * o;
+    }
   }
-  out(kOutOpacity, g, 0, dop, op_pre);
+  if (!comp) out(kOutOpacity, g, 0, dop, op_pre);
   const bool any = dm0 != 0.f || dm1 != 0.f || G[0] != 0.f || G[1] != 0.f || G[2] != 0.f ||
-                   G[3] != 0.f || acc[9] != 0.f;
+                   G[3] != 0.f || acc[9] != 0.f || comp;
   const bool raw = kHot || a.g.cov3d == nullptr;
   if (!any) {
     const float xv[3] = {xw, yw, zw};
@@ -687,7 +712,8 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
       JCn[i * 3 + j] = Jd[i * 3] * C[j] + Jd[i * 3 + 1] * C[3 + j] + Jd[i * 3 + 2] * C[6 + j];
     }
   double Q[4] = {Qf.x, Qf.y, Qf.z, Qf.w};
-  if (raw) {  // the conic of the double Sigma (the forward's is inv of an fp32 cov2d: off by eps cond(cov2d))
+  [[maybe_unused]] double V0[4] = {0.0, 0.0, 0.0, 0.0}, detV = 1.0;  // (kFilter) J C J^T + 1e-6 I, det(V0 + s I)
+  if (raw || (kFilter && comp)) {
     double V[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -696,14 +722,41 @@ __device__ __forceinline__ void project_bwd_one(const gs_project_bwd_args &a, in
         V[i * 2 + j] = JCn[i * 3] * Jd[j * 3] + JCn[i * 3 + 1] * Jd[j * 3 + 1] + JCn[i * 3 + 2] * Jd[j * 3 + 2];
     V[0] += 1e-6;
     V[3] += 1e-6;
-    const double idet = 1.0 / (V[0] * V[3] - V[1] * V[2]);
-    Q[0] = V[3] * idet; Q[1] = -V[1] * idet; Q[2] = -V[2] * idet; Q[3] = V[0] * idet;
+    if constexpr (kFilter) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) V0[k] = V[k];
+      V[0] += (double)a.filter.variance;
+      V[3] += (double)a.filter.variance;
+      detV = V[0] * V[3] - V[1] * V[2];
+    }
+    if (raw) {  // the conic of the double Sigma (the forward's is inv of an fp32 cov2d: off by eps cond(cov2d))
+      const double idet = 1.0 / (V[0] * V[3] - V[1] * V[2]);
+      Q[0] = V[3] * idet; Q[1] = -V[1] * idet; Q[2] = -V[2] * idet; Q[3] = V[0] * idet;
+    }
   }
   // d cov2d = -Q^T G Q^T (inverse backward)
   const double QG0 = Q[0] * G[0] + Q[2] * G[2], QG1 = Q[0] * G[1] + Q[2] * G[3];
   const double QG2 = Q[1] * G[0] + Q[3] * G[2], QG3 = Q[1] * G[1] + Q[3] * G[3];
-  const double dVd[4] = {-(QG0 * Q[0] + QG1 * Q[1]), -(QG0 * Q[2] + QG1 * Q[3]), -(QG2 * Q[0] + QG3 * Q[1]),
-                         -(QG2 * Q[2] + QG3 * Q[3])};
+  double dVd[4] = {-(QG0 * Q[0] + QG1 * Q[1]), -(QG0 * Q[2] + QG1 * Q[3]), -(QG2 * Q[0] + QG3 * Q[1]),
+                   -(QG2 * Q[2] + QG3 * Q[3])};
+  if constexpr (kFilter) {
+    if (comp) {
+      // rho = sqrt(max(r, floor)), r = det V0 / det V: d_opacity = acc[5] rho, and
+      // d_rho = acc[5] opacity reaches V0 (V = V0 + s I: dV = dV0) where the floor
+      // does not bind -- d r / d V0 = adj(V0)^T / det V - r adj(V)^T / det V
+      const double r = (V0[0] * V0[3] - V0[1] * V0[2]) / detV;
+      const double rho = sqrt(fmax(r, kRhoFloor));
+      out(kOutOpacity, g, 0, (float)((double)acc[5] * rho) * op_chain, op_pre);
+      if (r > kRhoFloor) {
+        const double dr = (double)acc[5] * (double)op_val / (2.0 * rho) / detV;
+        const double s = (double)a.filter.variance;
+        dVd[0] += dr * (V0[3] - r * (V0[3] + s));
+        dVd[1] += dr * (r - 1.0) * V0[2];
+        dVd[2] += dr * (r - 1.0) * V0[1];
+        dVd[3] += dr * (V0[0] - r * (V0[0] + s));
+      }
+    }
+  }
   double dJ[6];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -853,7 +906,7 @@ __device__ __forceinline__ void pose_block_sum(double v[kPoseVals], double (&red
   __syncthreads();
 }
 
-template <bool kHot, bool kAdam = false, bool kPose = false>
+template <bool kHot, bool kAdam = false, bool kPose = false, bool kFilter = false>
 __global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a,
                                                         std::conditional_t<kPose, PoseArgs, FusedAdamArgs> fa = {}) {
   static_assert(!kPose || (!kHot && !kAdam), "the pose reduction is the generic instantiation's");
@@ -881,7 +934,7 @@ __global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a,
   };
   if constexpr (kAdam) {
     AdamOut out;
-    project_bwd_one<kHot>(a, g, sums, out);
+    project_bwd_one<kHot, false, kFilter>(a, g, sums, out);
     out.flush(fa, g);
   } else if constexpr (kPose) {
     __shared__ double red[kBlock / kWave][kPoseRow], tot[kPoseRow];
@@ -890,13 +943,13 @@ __global__ __launch_bounds__(kBlock) void k_project_bwd(gs_project_bwd_args a,
     for (int q = 0; q < kPoseVals; ++q) pose[q] = 0.0;
     if (k < a.g.n) {
       GradsOut out{a};
-      project_bwd_one<false, true>(a, g, sums, out, pose);
+      project_bwd_one<false, true, kFilter>(a, g, sums, out, pose);
     }
     pose_block_sum(pose, red, tot);
     if (threadIdx.x < kPoseRow) fa.partials[(size_t)blockIdx.x * kPoseRow + threadIdx.x] = tot[threadIdx.x];
   } else {
     GradsOut out{a};
-    project_bwd_one<kHot>(a, g, sums, out);
+    project_bwd_one<kHot, false, kFilter>(a, g, sums, out);
   }
 }
 
@@ -940,6 +993,10 @@ bool rect_ok(const gs_camera &c) {
   return (span < tiles_x ? span : tiles_x) <= GS_MAX_RECT_TILES;
 }
 
+// gs_screen_filter's argument check: a finite variance >= 0
+const char *const kFilterMsg = "%s: filter.variance must be finite and >= 0";
+bool filter_ok(const gs_screen_filter &f) { return f.variance >= 0.f && __builtin_isfinite(f.variance); }
+
 // the gather's launch, for gs_gather_partials and the backward entry points
 gs_status launch_gather(const gs_project_bwd_args *a, int accumulate, hipStream_t s) {
   const uint32_t ng = (uint32_t)a->partial_groups;
@@ -982,6 +1039,7 @@ extern "C" {
 
 gs_status gs_project_forward(const gs_project_args *a, gs_stream_t stream) {
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_project_forward");
+  if (!filter_ok(a->filter)) return gs_internal_fail(GS_ERR_INVALID_ARG, kFilterMsg, "gs_project_forward");
   if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, "gs_project_forward");
   if (!rect_ok(a->cam))
     return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: radius_min <= radius_max, finite, with rectangles of at most 256 tiles in x "
@@ -997,10 +1055,18 @@ gs_status gs_project_forward(const gs_project_args *a, gs_stream_t stream) {
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: need cov3d or scaling+rotation", "gs_project_forward");
   if (a->g.sh_degree < 0 || a->g.sh_degree > 3 || (a->g.sh_degree > 0 && !a->g.sh_rest))
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: sh_degree must be 0..3, with sh_rest when > 0", "gs_project_forward");
-  if (!a->g.cov3d && a->g.sh_degree == 0)
-    k_project_fwd<true><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a);
-  else
-    k_project_fwd<false><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a);
+  const bool hot = !a->g.cov3d && a->g.sh_degree == 0;
+  const unsigned blocks = div_up(a->g.n, kBlock);
+  if (a->filter.variance > 0.f) {
+    if (hot)
+      k_project_fwd<true, true><<<blocks, kBlock, 0, s>>>(*a);
+    else
+      k_project_fwd<false, true><<<blocks, kBlock, 0, s>>>(*a);
+  } else if (hot) {
+    k_project_fwd<true><<<blocks, kBlock, 0, s>>>(*a);
+  } else {
+    k_project_fwd<false><<<blocks, kBlock, 0, s>>>(*a);
+  }
   return gs_internal_check_launch("gs_project_forward");
 }
 
@@ -1015,6 +1081,7 @@ gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, g
 
 gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) {
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_project_backward");
+  if (!filter_ok(a->filter)) return gs_internal_fail(GS_ERR_INVALID_ARG, kFilterMsg, "gs_project_backward");
   if (a->g.n <= 0) return GS_OK;
   if (gs_status st = check_project_bwd(a, "gs_project_backward")) return st;
   hipStream_t s = (hipStream_t)stream;
@@ -1023,10 +1090,17 @@ gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) 
     gs_status st = launch_gather(a, 0, s);
     if (st) return st;
   }
-  if (hot)
-    k_project_bwd<true><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a);
-  else
-    k_project_bwd<false><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a);
+  const unsigned blocks = div_up(a->g.n, kBlock);
+  if (a->filter.variance > 0.f) {
+    if (hot)
+      k_project_bwd<true, false, false, true><<<blocks, kBlock, 0, s>>>(*a);
+    else
+      k_project_bwd<false, false, false, true><<<blocks, kBlock, 0, s>>>(*a);
+  } else if (hot) {
+    k_project_bwd<true><<<blocks, kBlock, 0, s>>>(*a);
+  } else {
+    k_project_bwd<false><<<blocks, kBlock, 0, s>>>(*a);
+  }
   return gs_internal_check_launch("gs_project_backward");
 }
 
@@ -1034,6 +1108,7 @@ gs_status gs_project_backward_pose(const gs_project_pose_args *p, gs_stream_t st
   static const char *what = "gs_project_backward_pose";
   if (!p) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
   const gs_project_bwd_args *a = &p->bwd;
+  if (!filter_ok(a->filter)) return gs_internal_fail(GS_ERR_INVALID_ARG, kFilterMsg, what);
   if (!p->d_view) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null d_view", what);
   if (a->order)
     return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: the pose reduction walks the Gaussians in index order (order must be NULL)",
@@ -1053,7 +1128,10 @@ gs_status gs_project_backward_pose(const gs_project_pose_args *p, gs_stream_t st
     gs_status st = launch_gather(a, 0, s);
     if (st) return st;
   }
-  k_project_bwd<false, false, true><<<(unsigned)blocks, kBlock, 0, s>>>(*a, PoseArgs{p->pose_partials});
+  if (a->filter.variance > 0.f)
+    k_project_bwd<false, false, true, true><<<(unsigned)blocks, kBlock, 0, s>>>(*a, PoseArgs{p->pose_partials});
+  else
+    k_project_bwd<false, false, true><<<(unsigned)blocks, kBlock, 0, s>>>(*a, PoseArgs{p->pose_partials});
   if (gs_status st = gs_internal_check_launch(what)) return st;
   PoseView view;
   memcpy(view.v, a->cam.view, sizeof(view.v));
@@ -1064,6 +1142,7 @@ gs_status gs_project_backward_pose(const gs_project_pose_args *p, gs_stream_t st
 gs_status gs_project_backward_adam(const gs_project_bwd_args *a, const gs_adam_args *adam, gs_stream_t stream) {
   static const char *what = "gs_project_backward_adam";
   if (!a || !adam) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (!filter_ok(a->filter)) return gs_internal_fail(GS_ERR_INVALID_ARG, kFilterMsg, what);
   if (a->g.n <= 0) return GS_OK;
   // the training configuration only (k_project_bwd<kHot>): raw scale /
   // rotation, DC colour, blend sums, no viewspace / conic cotangents
@@ -1108,7 +1187,10 @@ gs_status gs_project_backward_adam(const gs_project_bwd_args *a, const gs_adam_a
     gs_status st = launch_gather(a, 0, s);
     if (st) return st;
   }
-  k_project_bwd<true, true><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a, f);
+  if (a->filter.variance > 0.f)
+    k_project_bwd<true, true, false, true><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a, f);
+  else
+    k_project_bwd<true, true><<<div_up(a->g.n, kBlock), kBlock, 0, s>>>(*a, f);
   return gs_internal_check_launch(what);
 }
 

@@ -148,6 +148,8 @@ size_t gs_tile_workspace_bytes(int64_t capacity, int32_t num_tiles, int32_t live
 gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
   static const char *what = "gs_render_forward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (!(a->filter.variance >= 0.f) || !__builtin_isfinite(a->filter.variance))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: filter.variance must be finite and >= 0", what);
   const int32_t n = a->g.n, W = a->cam.image_width, H = a->cam.image_height, L = a->cam.tile_size;
   if (n < 0 || W <= 0 || H <= 0 || L < 1) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad sizes", what);
   const int32_t tiles_x = div_up_i(W, L), tiles_y = div_up_i(H, L), tiles = tiles_x * tiles_y;
@@ -213,6 +215,7 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
     pa.key_base = a->key_base;
     pa.key_bits = a->key_bits;
     pa.key_minmax = key_minmax;
+    pa.filter = a->filter;
     if ((st = gs_project_forward(&pa, stream))) return st;
     if (n == 0) return GS_OK;
     int32_t alt = 0;
@@ -345,6 +348,8 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
 gs_status gs_render_backward(gs_render_bwd_args *a, gs_stream_t stream) {
   static const char *what = "gs_render_backward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (!(a->filter.variance >= 0.f) || !__builtin_isfinite(a->filter.variance))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: filter.variance must be finite and >= 0", what);
   const int32_t n = a->g.n, W = a->cam.image_width, H = a->cam.image_height, L = a->cam.tile_size;
   if (n < 0 || W <= 0 || H <= 0 || L < 1) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad sizes", what);
   const int32_t tiles_x = div_up_i(W, L), tiles_y = div_up_i(H, L), tiles = tiles_x * tiles_y;
@@ -455,6 +460,7 @@ gs_status gs_render_backward(gs_render_bwd_args *a, gs_stream_t stream) {
   pb.d_opacity = a->d_opacity;
   pb.d_sh_rest = a->d_sh_rest;
   pb.grad_sums = pixel_grads ? grad_sums : nullptr;  // (the sums are there: no gather here)
+  pb.filter = a->filter;
   if (a->fused_adam) return gs_project_backward_adam(&pb, a->fused_adam, stream);
   return gs_project_backward(&pb, stream);
 }

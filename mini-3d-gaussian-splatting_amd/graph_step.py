@@ -84,6 +84,8 @@ class GraphedStep:
                                  world_view=wv)
         if self.cam.tile_size != N.GS_DEFAULT_TILE:
             raise ValueError("GraphedStep renders the default 16-px tile")
+        if self.cam.screen_filter > 0:
+            raise ValueError("GraphedStep renders without a screen filter")
         sh = settings.sh_degree if settings.sh_degree is not None else int(getattr(model, "active_sh_degree", 0))
         if sh:
             raise ValueError("GraphedStep renders DC colour (sh_degree 0)")

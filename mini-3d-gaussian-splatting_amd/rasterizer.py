@@ -44,6 +44,13 @@ class CameraParams:
     radius_min: float = 0.01
     radius_max: float = 50.0
     tile_size: int = N.GS_DEFAULT_TILE  # GaussianRenderer(tile_size) (renderer.py:24,261-264)
+    # the screen-space low-pass filter (gs_screen_filter; not in the reference): cov2d + screen_filter I
+    # (px^2, 0 = off), and with filter_compensate the opacity scaled so that a splat keeps its energy
+    screen_filter: float = 0.0
+    filter_compensate: bool = True
+
+    def __post_init__(self):
+        check_screen_filter(self.screen_filter)
 
     @property
     def tiles_x(self) -> int:
@@ -76,13 +83,19 @@ class CameraParams:
         ~5-10 us of host time per frame; callers copy it into their
         argument structs and never modify it)."""
         key = (self.image_width, self.image_height, self.fx, self.fy, self.cx, self.cy, self.view, self.bg,
-               self.radius_min, self.radius_max, self.tile_size)
+               self.radius_min, self.radius_max, self.tile_size, self.screen_filter, self.filter_compensate)
         c = _CAM_STRUCTS.get(key)
         if c is None:
             if len(_CAM_STRUCTS) >= 4096:
                 _CAM_STRUCTS.clear()
             c = _CAM_STRUCTS[key] = self._build_struct()
         return c
+
+    def filter_struct(self) -> N.GsScreenFilter:
+        """The ABI filter for the trailing field of the projection's and the
+        frame entry points' arguments (all zero when off)."""
+        s = float(self.screen_filter)
+        return N.GsScreenFilter(s, 1 if self.filter_compensate else 0) if s > 0.0 else _NO_FILTER
 
     def _build_struct(self) -> N.GsCamera:
         c = N.GsCamera()
@@ -105,6 +118,14 @@ class CameraParams:
         return tuple(-(R[0][j] * t[0] + R[1][j] * t[1] + R[2][j] * t[2]) for j in range(3))
 
 
+def check_screen_filter(variance) -> None:
+    """ValueError for a screen filter variance no render can use (negative, NaN or infinite)."""
+    v = float(variance)
+    if not (v >= 0.0 and math.isfinite(v)):
+        raise ValueError(f"screen_filter must be a finite variance >= 0 (px^2), got {variance!r}")
+
+
+_NO_FILTER = N.GsScreenFilter()  # (shared, never modified: callers copy it into their argument structs)
 _GROUPS: dict = {}
 _CAM_STRUCTS: dict = {}  # CameraParams values -> GsCamera (CameraParams.to_struct)
 
@@ -654,6 +675,8 @@ def _bind_frame_args(fa: "N.GsRenderFwdArgs", cam: CameraParams, gst, gaussian_o
     """The fields of gs_render_forward's arguments every caller fills alike:
     camera, Gaussians, the seven outputs and the frame workspace."""
     fa.cam, fa.g = cam.to_struct(), gst
+    if cam.screen_filter:  # (fa is zeroed: no filter)
+        fa.filter = cam.filter_struct()
     fa.means2d, fa.conics, fa.radii, fa.vis = (t.data_ptr() for t in gaussian_outs)
     fa.image, fa.alpha, fa.depth = (t.data_ptr() for t in pixel_outs)
     fb = fa.fb
@@ -764,7 +787,7 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
     StageTimer.mark("project_fwd")
     pa = N.GsProjectArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(radii), N.ptr(vis), N.ptr(records),
-                         N.ptr(rects), N.ptr(keys[0]), key_base, key_bits, N.ptr(key_minmax))
+                         N.ptr(rects), N.ptr(keys[0]), key_base, key_bits, N.ptr(key_minmax), cam.filter_struct())
     N.check(lib.gs_project_forward(C.byref(pa), s), "gs_project_forward")
 
     fr = _Frame()
@@ -977,7 +1000,7 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                             # order coalesces the slot reads but scatters 10 arrays (measured 2.4x slower)
                             N.ptr(fr.pair_offset), None, N.ptr(pair_grads), N.ptr(gm), N.ptr(gc), N.ptr(d_xyz),
                             N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col), N.ptr(d_op), N.ptr(d_sh),
-                            N.ptr(slot_live), N.ptr(grad_sums), fr.groups)
+                            N.ptr(slot_live), N.ptr(grad_sums), fr.groups, cam.filter_struct())
     StageTimer.mark("project_bwd")
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
     if density is not None:
@@ -1081,6 +1104,7 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     ba.cam, ba.fb, ba.M, ba.T, ba.tile_alt = fa.cam, fa.fb, fr.M, fr.T, fa.tile_alt
     # (the forward's Gaussians: the tensors autograd saved for this backward)
     ba.g, ba.means2d, ba.conics, ba.vis = fa.g, fa.means2d, fa.conics, fa.vis
+    ba.filter = fa.filter
     pair_grads = None
     if fr.M > 0 and fr.T > 0 and pixel_grads:
         g_image, g_alpha, g_depth, image, alpha, depth = _pixel_cotangents(cam, g_image, g_alpha, g_depth, outputs,
@@ -1118,7 +1142,7 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     pb = N.GsProjectBwdArgs(fa.cam, ba.g, N.ptr(means2d), N.ptr(conics), fa.vis, fws + fo[1], fws + fo[8], None,
                             None, N.ptr(gm),
                             N.ptr(gc), N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col),
-                            N.ptr(d_op), N.ptr(d_sh), None, sums, 0)
+                            N.ptr(d_op), N.ptr(d_sh), None, sums, 0, fa.filter)
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
     if density is not None:
         _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], sums, gm, s)

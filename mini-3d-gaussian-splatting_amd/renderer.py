@@ -28,6 +28,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     "features": F [N, C] composited with the colour pass's own weights.
   * `render(..., density_stats=S)` (not in the reference) adds the view to the
     density-control statistics S at the end of its backward (DensityStats).
+  * `settings.screen_filter` (not in the reference; default 0 = off) low-pass
+    filters every splat in screen space, cov2d + s I, and with
+    `settings.filter_compensate` keeps its energy (anti-aliasing).
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
     switches on view-dependent SH colour; at 0 -- the default for the
     reference's own model and stubs -- colours are the reference's
@@ -42,7 +45,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _native as N
-from .rasterizer import CameraParams, DensityStats, rasterize
+from .rasterizer import CameraParams, DensityStats, check_screen_filter, rasterize
 
 
 @dataclass
@@ -58,6 +61,20 @@ class RenderSettings:
     # else 0 (the reference's behaviour).  1..3 evaluates SH of that degree from
     # get_features[:, 1:, :] (include/gsplat_mi355x.h, gs_gaussians).
     sh_degree: Optional[int] = None
+    # Screen-space low-pass filter (anti-aliasing; not in the reference): the
+    # variance s in px^2 added to every projected covariance, cov2d + s I, before
+    # the conic, the radius and the culling (include/gsplat_mi355x.h,
+    # gs_screen_filter).  0 is off -- the reference's projection, bit for bit;
+    # 0.3 is 3DGS's dilation, 0.1 Mip-Splatting's.  A negative, NaN or infinite
+    # value is a ValueError.
+    screen_filter: float = 0.0
+    # with the filter: scale each opacity by sqrt(det cov2d / det(cov2d + s I)), so
+    # that a splat keeps its energy (Mip-Splatting / gsplat "antialiased"); False
+    # is the plain 3DGS dilation.  Read only when screen_filter > 0.
+    filter_compensate: bool = True
+
+    def __post_init__(self):
+        check_screen_filter(self.screen_filter)
 
 
 def _world_view(camera) -> torch.Tensor:
@@ -110,7 +127,8 @@ def camera_params(camera, settings: RenderSettings, radius_min=0.01, radius_max=
     bg = tuple(_host_f32(settings.bg_color, 3))
     tile = effective_tile(tile_size, settings.image_width, settings.image_height)
     return CameraParams(int(settings.image_width), int(settings.image_height), fx, fy, W * 0.5, H * 0.5,
-                        view, bg, float(radius_min), float(radius_max), tile)
+                        view, bg, float(radius_min), float(radius_max), tile,
+                        float(getattr(settings, "screen_filter", 0.0)), bool(getattr(settings, "filter_compensate", True)))
 
 
 class GaussianRenderer:

@@ -93,7 +93,9 @@ class GaussianTrainer:
         return float(self.dataset.get_scene_info()["radius"])
 
     def _settings(self, cam) -> RenderSettings:
-        return RenderSettings(image_height=cam._height, image_width=cam._width, bg_color=torch.zeros(3))
+        c = self.config
+        return RenderSettings(image_height=cam._height, image_width=cam._width, bg_color=torch.zeros(3),
+                              screen_filter=c.screen_filter, filter_compensate=c.filter_compensate)
 
     def _camera_for(self, it: int):
         cams = self.dataset.get_train_cameras()
