@@ -495,6 +495,75 @@ typedef struct gs_feature_gather_args {
 } gs_feature_gather_args;
 gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_t stream);
 
+/* ---- Per-Gaussian blend contribution statistics ---------------------------
+ * How much each Gaussian contributes to a frame: a third replay of the
+ * colour forward (ranges / sorted_gauss / records with pair offsets /
+ * cell_neval / live_bits, as the feature kernels; any tile_size; live_bits
+ * NULL: every entry of a cell's evaluated prefix), one 64-lane workgroup per
+ * (tile, 8x8 cell) of the cell batch [cell_begin, cell_begin + cell_count).
+ * With c the forward's own contribution weight of an entry at a pixel
+ * (c = (1 - A) alpha; +0 for a lane outside the tile or image, a skipped
+ * pair or a terminated pixel), every replayed (entry, cell) writes
+ *   partials[(slot G + q) GS_CONTRIB_STRIDE + 0] = sum over the cell's pixels of c (a fixed order)
+ *                                            + 1] = max over the cell's pixels of c
+ *                                            + 2] = pixels with c > 0 (a float, exact, <= 64)
+ *                                            + 3] = 0 (reserved)
+ *   slot_live[slot G + q] = 1
+ * (one aligned 16-byte store; slot, G = cell_count and q as in
+ * gs_blend_features_backward; cells that do not replay an entry write
+ * nothing; no atomics).
+ * dominant_id / dominant_weight (both or neither), [H*W]: per pixel of the
+ * image the Gaussian of the entry with the largest c there (the first in
+ * list order among equals) and that c; -1 / 0 where no entry has c > 0.
+ * Every pixel of the batch's cells is written, those of empty tiles too.
+ * n == 0 or num_pairs == 0: GS_OK, no partial is written, the maps are
+ * filled with -1 / 0. */
+#define GS_CONTRIB_STRIDE 4
+typedef struct gs_contrib_args {
+  gs_camera cam;
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;
+  const uint32_t *sorted_gauss;
+  const float *records;         /* with pair offsets (gs_bin_emit) */
+  const uint32_t *cell_neval;
+  const uint64_t *live_bits;    /* or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;        /* n */
+  float *partials;              /* [T, G, GS_CONTRIB_STRIDE], 16-byte aligned */
+  uint8_t *slot_live;           /* [T, G], zeroed by the caller */
+  int32_t cell_begin;           /* the batch's first cell */
+  int32_t cell_count;           /* the batch's cells (0 with cell_begin 0: the whole tile) */
+  int32_t *dominant_id;         /* [H*W] or NULL */
+  float *dominant_weight;       /* [H*W] or NULL (with dominant_id) */
+} gs_contrib_args;
+gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream);
+
+/* One view's (or cell batch's) partials added to the running statistics:
+ * per Gaussian g < n with vis[g] != 0, over its slots [pair_offset[g], +
+ * touches) and the partial_groups groups slot_live flags, s = the sums added
+ * in gs_gather_partials' slot, group and lane-tree order, m = the max,
+ * k = the counts added; then
+ *   weight_sum[g] += s, weight_max[g] = fmaxf(weight_max[g], m),
+ *   pixels[g] += k, views[g] += first_batch ? 1 : 0.
+ * A row with vis[g] == 0 is neither read nor written.  first_batch: 1 for a
+ * view's first cell batch, 0 for its later ones. */
+typedef struct gs_contrib_gather_args {
+  int32_t n;
+  const uint8_t *vis;           /* as gs_project_bwd_args */
+  const uint32_t *rects;
+  const uint32_t *pair_offset;
+  const float *partials;        /* [T, G, GS_CONTRIB_STRIDE] */
+  const uint8_t *slot_live;     /* [T, G] */
+  int32_t partial_groups;       /* G */
+  int32_t first_batch;
+  float *weight_sum;            /* [n] */
+  float *weight_max;            /* [n] */
+  int64_t *pixels;              /* [n] */
+  int32_t *views;               /* [n] */
+} gs_contrib_gather_args;
+gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t stream);
+
 /* ---- Backward of the projection ----------------------------------------
  * Sums each Gaussian's slot partials (slots [pair_offset[g], pair_offset[g]
  * + touches), the groups slot_live flags), adds cotangents on the viewspace_points /

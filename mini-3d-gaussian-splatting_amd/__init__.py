@@ -8,7 +8,7 @@ library libgsplat_mi355x.so (csrc/, C ABI in include/gsplat_mi355x.h).
 from .renderer import GaussianRenderer, RenderSettings, camera_params  # noqa: F401
 from .gaussian_model import GaussianModel, build_rotation_matrix  # noqa: F401
 from .camera import Camera, CameraUtils  # noqa: F401
-from .rasterizer import CameraParams, DensityStats, rasterize  # noqa: F401
+from .rasterizer import CameraParams, ContributionStats, DensityStats, rasterize  # noqa: F401
 from .loss import SSIMLoss, GaussianLoss, photometric_loss  # noqa: F401
 from .config import TrainingConfig, ConfigManager  # noqa: F401
 from .dataset import CameraDataset, NeRFSyntheticDataset, COLMAPDataset, load_dataset  # noqa: F401
@@ -20,4 +20,5 @@ from . import _native, synthetic, distributed, optim, loss, dataset, trainer, gr
 __all__ = ["GaussianRenderer", "RenderSettings", "GaussianModel", "Camera", "CameraUtils",
            "CameraParams", "rasterize", "camera_params", "SSIMLoss", "GaussianLoss", "photometric_loss",
            "TrainingConfig", "ConfigManager", "CameraDataset", "NeRFSyntheticDataset", "COLMAPDataset",
-           "load_dataset", "GaussianTrainer", "GraphedStep", "CameraPose", "se3_exp", "DensityStats"]
+           "load_dataset", "GaussianTrainer", "GraphedStep", "CameraPose", "se3_exp", "DensityStats",
+           "ContributionStats"]

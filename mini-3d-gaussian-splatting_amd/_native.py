@@ -148,6 +148,27 @@ class GsFeatureGatherArgs(C.Structure):
     ]
 
 
+GS_CONTRIB_STRIDE = 4  # floats per contribution partial: (sum, max, count, reserved), one 16-byte store
+
+
+class GsContribArgs(C.Structure):
+    _fields_ = [
+        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
+        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
+        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("partials", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32), ("cell_count", C.c_int32),
+        ("dominant_id", _vp), ("dominant_weight", _vp),
+    ]
+
+
+class GsContribGatherArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("vis", _vp), ("rects", _vp), ("pair_offset", _vp), ("partials", _vp),
+        ("slot_live", _vp), ("partial_groups", C.c_int32), ("first_batch", C.c_int32), ("weight_sum", _vp),
+        ("weight_max", _vp), ("pixels", _vp), ("views", _vp),
+    ]
+
+
 GS_POSE_ROW = 16  # doubles per row of gs_project_pose_args.pose_partials; one row per 256 Gaussians
 GS_POSE_BLOCK = 256
 
@@ -256,6 +277,7 @@ EXPORTS = (
     "gs_render_backward", "gs_frame_offsets", "gs_tile_offsets", "gs_adam_step", "gs_project_backward_adam", "gs_loss_workspace_bytes", "gs_loss_forward", "gs_loss_backward",
     "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit", "gs_density_accumulate",
     "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
+    "gs_blend_contributions", "gs_contrib_accumulate",
 )
 
 _lib = None
@@ -320,10 +342,13 @@ def _declare(lib):
     lib.gs_blend_features_forward.argtypes = [P(GsFeatureFwdArgs), _vp]
     lib.gs_blend_features_backward.argtypes = [P(GsFeatureBwdArgs), _vp]
     lib.gs_gather_feature_partials.argtypes = [P(GsFeatureGatherArgs), _vp]
+    lib.gs_blend_contributions.argtypes = [P(GsContribArgs), _vp]
+    lib.gs_contrib_accumulate.argtypes = [P(GsContribGatherArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
-              "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials"):
+              "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
+              "gs_blend_contributions", "gs_contrib_accumulate"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -67,6 +67,16 @@ class TrainingConfig:
     # opacities are scaled so that a filtered splat keeps its energy
     screen_filter: float = 0.0
     filter_compensate: bool = True
+    # contribution pruning (GaussianTrainer.compact): at these iterations, after the optimizer step,
+    # every training camera is rendered and the Gaussians whose largest blend weight over all of them
+    # is not above the threshold are dropped (0.01: RadSplat's default); () = never
+    contribution_prune_iterations: tuple = ()
+    contribution_prune_threshold: float = 0.01
+
+    def __post_init__(self):
+        # (a YAML file holds the iterations as a list)
+        if isinstance(self.contribution_prune_iterations, list):
+            self.contribution_prune_iterations = tuple(self.contribution_prune_iterations)
 
     def check(self) -> None:
         """Values no run can use (the trainer asks at setup)."""
@@ -75,6 +85,12 @@ class TrainingConfig:
         s = float(self.screen_filter)
         if not (s >= 0.0 and s != float("inf")):
             raise ValueError(f"screen_filter must be a finite variance >= 0 (px^2), got {self.screen_filter!r}")
+        if not float(self.contribution_prune_threshold) >= 0.0:
+            raise ValueError(f"contribution_prune_threshold must be >= 0, got {self.contribution_prune_threshold!r}")
+        its = self.contribution_prune_iterations
+        if isinstance(its, (str, bytes)) or not all(isinstance(i, int) and not isinstance(i, bool) and i > 0
+                                                    for i in its):
+            raise ValueError(f"contribution_prune_iterations must hold positive iteration numbers, got {its!r}")
 
 
 DENSIFY_CRITERIA = ("xyz_grad", "screen")

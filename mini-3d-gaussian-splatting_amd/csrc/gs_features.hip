@@ -2,6 +2,8 @@
 //   k_feat_fwd     features_out[k, p] = sum_i c_i F[g_i, k]   (the weights of renderer.py:319-353)
 //   k_feat_bwd     its backward, per-pair grad slots in k_blend_bwd's layout
 //   k_gather_feat  a chunk's partials summed per Gaussian (k_gather_slots' order)
+//   k_contrib      per (entry, cell) the sum, max and count of c over the cell's pixels, and each
+//                  pixel's strongest contributor; k_contrib_gather adds them up per Gaussian
 // Neither blend kernel decides anything of its own: both replay the colour
 // forward (k_blend_fwd, gs_blend.hip) over the state it saved -- ranges,
 // sorted_gauss, records, cell_neval, live_bits -- with the operations
@@ -459,6 +461,192 @@ __global__ __launch_bounds__(kBlock) void k_gather_feat(gs_feature_gather_args a
     if (k < a.channel_count) df[k] = a.feature_accumulate ? df[k] + acc[6 + k] : acc[6 + k];
 }
 
+// ==================================================== contributions =======
+// A third replay, with no payload: how much every entry contributes.
+//  A (pixel-parallel), per live entry: the pixel's c into a group buffer,
+//    and the pixel's largest c so far with its Gaussian (strict >: the first
+//    entry in list order wins).
+//  B (entry-parallel), per group of up to kBwdGroup live entries: lanes
+//    8j..8j+7 reduce entry j's 64 pixels -- lane 8j + x takes column x, rows
+//    0..7 in order -- to (sum, max, count) and finish with 3 DPP steps each.
+constexpr int kCtbRow = kWave + 8;  // rows padded to 72 floats: the 8 entries' columns fall in 64 different banks
+
+__device__ __forceinline__ float oct_max(float v) {
+  v = fmaxf(v, dpp_row<0xB1>(v));
+  v = fmaxf(v, dpp_row<0x4E>(v));
+  v = fmaxf(v, dpp_row<0x141>(v));
+  return v;
+}
+
+__global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
+  __shared__ float s_c[kBwdGroup][kCtbRow];  // per group entry and pixel: c
+  __shared__ float4 s_wrec[kBwdGroup * 2];   // the group's records: (mx my h00 h11) (ho o slot gid)
+  Replay r;
+  const int ncell = a.cell_count;
+  const bool any = replay_setup(r, a.cam, a.tiles_x, a.tiles_y, ncell, a.cell_begin, a.ranges,
+                                (uint32_t)a.num_pairs, a.cell_neval, a.live_bits, a.live_words);
+  if (r.tile >= a.tiles_x * a.tiles_y) return;
+  const int lane = threadIdx.x;
+  float best = 0.f;
+  int best_id = -1;
+  if (any) {
+    const int qb = r.quad - a.cell_begin;  // the cell's partial group
+    const uint32_t ngauss = (uint32_t)a.num_gaussians;
+    const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+    const float fx = (float)r.px, fy = (float)r.py;
+    float A = 0.f, T1 = 1.f;
+    bool run = r.inside;
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
+    uint32_t gcur = 0u;
+    auto fetch = [&](uint32_t wd, unsigned long long m) {
+      if ((m >> lane) & 1ull) {
+        gcur = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+        r0 = recs[3 * (size_t)gcur];
+        r1 = recs[3 * (size_t)gcur + 1];
+        r2 = recs[3 * (size_t)gcur + 2];
+      }
+    };
+    auto phase_b = [&](int k) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
+      const int j = lane / kBwdLanes, col = lane % kBwdLanes;
+      if (j < k) {
+        float sum = 0.f, mx = 0.f, cnt = 0.f;
+#pragma unroll
+        for (int row = 0; row < kBwdGroup; ++row) {
+          const float c = s_c[j][col + 8 * row];
+          sum += c;
+          mx = fmaxf(mx, c);
+          cnt += c > 0.f ? 1.f : 0.f;
+        }
+        sum = oct_sum(sum);
+        mx = oct_max(mx);
+        cnt = oct_sum(cnt);  // (small integers: exact)
+        if (col == 0) {
+          const uint32_t slot = __float_as_uint(s_wrec[2 * j + 1].z);
+          if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+            const size_t sq = (size_t)slot * (uint32_t)ncell + (uint32_t)qb;
+            reinterpret_cast<float4 *>(a.partials)[sq] = make_float4(sum, mx, cnt, 0.f);
+            a.slot_live[sq] = 1;
+          }
+        }
+      }
+    };
+    unsigned long long mcur = r.live_word(0);
+    fetch(0, mcur);
+    for (uint32_t wd = 0; wd < r.nwords; ++wd) {
+      // the entry's gradient slot, as k_feat_bwd forms it
+      const bool mine = (mcur >> lane) & 1ull;
+      const uint32_t info = __float_as_uint(r2.w);
+      const uint32_t slot = __float_as_uint(r2.z) + (r.ty - ((info >> 12) & 0xFFFu)) * ((info >> 24) + 1u) +
+                            (r.tx - (info & 0xFFFu));
+      const uint32_t rank =
+          __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
+      const float4 c0 = make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
+      const float4 c1 = make_float4(-0.5f * r1.x, r1.y, __uint_as_float(slot), __uint_as_float(gcur));
+      const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
+      fetch(wd + 1u, mnext);  // in flight while this word replays
+      unsigned long long m = mcur;
+      uint32_t kb = 0;  // packed position of the group's first entry
+      while (m) {
+        int k = 0;
+        // (the previous group's reads came before these writes in this wave's in-order LDS queue)
+        if (mine && rank - kb < (uint32_t)kBwdGroup) {
+          s_wrec[2 * (rank - kb)] = c0;
+          s_wrec[2 * (rank - kb) + 1] = c1;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
+#pragma unroll
+        for (int kk = 0; kk < kBwdGroup; ++kk) {
+          if (kk > 0 && !m) break;
+          m &= m - 1ull;
+          const float4 r0v = s_wrec[2 * kk], r1v = s_wrec[2 * kk + 1];
+          const float dx = fx - r0v.x, dy = fy - r0v.y;
+          const float t = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
+          const bool lv = run && !(t < kSkipT);
+          const float w = sat01(exp_blend(t));
+          const float ai = lv ? sat01(r1v.y * w) : 0.f;
+          const float c = T1 * ai;
+          if (c > best) {
+            best = c;
+            best_id = (int)__float_as_uint(r1v.w);
+          }
+          A = A + c;
+          T1 = 1.f - A;
+          run = run && A < kAlphaStop;
+          s_c[kk][lane] = c;
+          k = kk + 1;
+        }
+        phase_b(k);
+        kb += (uint32_t)k;
+      }
+      mcur = mnext;
+    }
+  }
+  if (a.dominant_id && r.inside) {
+    const size_t p = (size_t)r.py * a.cam.image_width + r.px;
+    a.dominant_id[p] = best_id;
+    a.dominant_weight[p] = best;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_contrib_empty(int32_t *id, float *weight, long long pixels) {
+  const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (p < pixels) {
+    id[p] = -1;
+    weight[p] = 0.f;
+  }
+}
+
+template <int LPG>
+__device__ __forceinline__ float lanes_max(float v) {
+  if constexpr (LPG == 8) return oct_max(v);
+  if constexpr (LPG == 4 || LPG == 2) {
+    v = fmaxf(v, dpp_row<0xB1>(v));
+    if constexpr (LPG == 4) v = fmaxf(v, dpp_row<0x4E>(v));
+  }
+  return v;
+}
+
+// k_gather_feat's walk and lane tree over the 16-byte contribution partials
+template <int QL, int HL>
+__global__ __launch_bounds__(kBlock) void k_contrib_gather(gs_contrib_gather_args a) {
+  constexpr int LPG = QL * HL;
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const int g = (int)(t / LPG);
+  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
+  const bool valid = g < a.n;
+  const uint32_t gi = valid ? (uint32_t)g : 0u;
+  const bool seen = valid && a.vis[gi];
+  const uint2 rect = reinterpret_cast<const uint2 *>(a.rects)[gi];
+  const int tx0 = (int)(rect.x & 0xFFFFu), tx1 = (int)(rect.x >> 16);
+  const int ty0 = (int)(rect.y & 0xFFFFu), ty1 = (int)(rect.y >> 16);
+  const size_t off = a.pair_offset[gi];
+  const uint32_t cnt = seen ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
+  const uint32_t ng = (uint32_t)a.partial_groups;
+  float s = 0.f, m = 0.f;
+  int ki = 0;  // (counts as integers: a Gaussian's total may pass 2^24)
+  for (uint32_t qc = (uint32_t)q; qc < ng; qc += QL) {
+    for (uint32_t e = (uint32_t)h; e < cnt; e += HL) {
+      const size_t at = (off + e) * ng + qc;
+      if (!a.slot_live[at]) continue;
+      const float4 v = reinterpret_cast<const float4 *>(a.partials)[at];
+      s += v.x;
+      m = fmaxf(m, v.y);
+      ki += (int)v.z;
+    }
+  }
+  s = lanes_sum<LPG>(s);
+  m = lanes_max<LPG>(m);
+  ki += __builtin_amdgcn_update_dpp(0, ki, 0xB1, 0xF, 0xF, true);
+  if constexpr (LPG >= 4) ki += __builtin_amdgcn_update_dpp(0, ki, 0x4E, 0xF, 0xF, true);
+  if constexpr (LPG == 8) ki += __builtin_amdgcn_update_dpp(0, ki, 0x141, 0xF, 0xF, true);
+  if ((t % LPG) != 0 || !seen) return;
+  a.weight_sum[g] = a.weight_sum[g] + s;
+  a.weight_max[g] = fmaxf(a.weight_max[g], m);
+  a.pixels[g] += (int64_t)ki;
+  a.views[g] += a.first_batch ? 1 : 0;
+}
+
 int cells_per_tile(int tile_size) {
   const int qx = (tile_size + GS_QUAD - 1) / GS_QUAD;
   return qx * qx;
@@ -544,6 +732,57 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
     k_gather_feat<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
   else
     k_gather_feat<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  return gs_internal_check_launch(me);
+}
+
+gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream) {
+  const char *me = "gs_blend_contributions";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
+  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
+  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
+  if (a->num_pairs < 0 || a->num_gaussians < 0)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or num_gaussians", me);
+  if (!a->ranges || !a->records || !a->cell_neval || !a->partials || !a->slot_live ||
+      (a->live_bits && a->live_words <= 0) || (a->num_pairs > 0 && !a->sorted_gauss))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (!a->dominant_id != !a->dominant_weight)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: dominant_id and dominant_weight go together", me);
+  const int cells = cells_per_tile(a->cam.tile_size);
+  gs_contrib_args b = *a;
+  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
+  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
+                "[0, gs_tile_quads(tile_size))", me);
+  const long long blocks = (long long)div_up((long long)b.tiles_x * b.tiles_y, 8) * 8LL * b.cell_count;
+  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  if (b.num_gaussians == 0 || b.num_pairs == 0) {
+    if (!b.dominant_id) return GS_OK;
+    const long long pixels = (long long)b.cam.image_width * b.cam.image_height;
+    k_contrib_empty<<<div_up(pixels, kBlock), kBlock, 0, (hipStream_t)stream>>>(b.dominant_id, b.dominant_weight, pixels);
+    return gs_internal_check_launch(me);
+  }
+  k_contrib<<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b);
+  return gs_internal_check_launch(me);
+}
+
+gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t stream) {
+  const char *me = "gs_contrib_accumulate";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
+  if (a->n < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative n", me);
+  if (!a->vis || !a->rects || !a->pair_offset || !a->partials || !a->slot_live || !a->weight_sum || !a->weight_max ||
+      !a->pixels || !a->views)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (a->partial_groups < 1) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: partial_groups < 1", me);
+  if (a->n == 0) return GS_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // (k_gather_slots' lanes per Gaussian for the same partial_groups)
+  if (a->partial_groups == 1)
+    k_contrib_gather<1, 4><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  else if (a->partial_groups == 2)
+    k_contrib_gather<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  else
+    k_contrib_gather<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
   return gs_internal_check_launch(me);
 }
 

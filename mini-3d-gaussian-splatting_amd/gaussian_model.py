@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
-from .rasterizer import DensityStats
+from .rasterizer import ContributionStats, DensityStats
 
 
 def build_rotation_matrix(q: torch.Tensor) -> torch.Tensor:
@@ -61,6 +61,7 @@ class GaussianModel(nn.Module):
         # the statistics the renderer fills (render(..., density_stats=)) and the "screen"
         # densification reads; zeros of the model's size wherever the three buffers above are re-made
         self.density_stats = DensityStats(0, self._xyz.device)
+        self._contribution_stats = None  # (made on first use: see contribution_stats)
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
         self.opacity_activation = torch.sigmoid
@@ -71,7 +72,19 @@ class GaussianModel(nn.Module):
         out = super()._apply(fn, *args, **kwargs)
         if self.density_stats.device != self._xyz.device:
             self.density_stats = DensityStats(self.get_num_points(), self._xyz.device)
+        if self._contribution_stats is not None and self._contribution_stats.device != self._xyz.device:
+            self._contribution_stats = None
         return out
+
+    @property
+    def contribution_stats(self) -> ContributionStats:
+        """The blend contribution statistics render(..., contribution_stats=)
+        fills, of the model's size on its device: made on first use, and made
+        anew (zeros) whenever the number of Gaussians changes."""
+        st = self._contribution_stats
+        if st is None or st.n != self.get_num_points() or st.device != self._xyz.device:
+            st = self._contribution_stats = ContributionStats(self.get_num_points(), self._xyz.device)
+        return st
 
     def oneup_sh_degree(self) -> None:
         """Raise the rendered SH degree by one, up to max_sh_degree."""
@@ -93,6 +106,7 @@ class GaussianModel(nn.Module):
         self.denom = torch.zeros(n, 1, device=dev)
         self.max_radii2D = torch.zeros(n, device=dev)
         self.density_stats = DensityStats(n, dev)
+        self._contribution_stats = None
 
     @torch.no_grad()
     def create_from_random(self, num_points: int, scene_extent: float = 1.0,
@@ -292,8 +306,25 @@ class GaussianModel(nn.Module):
         self.densify_and_prune(grad_threshold, scene_extent, split=False, clone=True, prune=False)
 
     @torch.no_grad()
-    def prune_points(self, mask: torch.Tensor) -> None:
-        """gaussian_model.py:181-197: keep the Gaussians where mask is True."""
+    def prune_points(self, mask: torch.Tensor, optimizer: Optional[torch.optim.Optimizer] = None) -> None:
+        """gaussian_model.py:181-197: keep the Gaussians where mask is True.
+        With `optimizer`, the Adam moments of the kept rows follow them, the
+        step counts stay, and its parameter references are replaced, as
+        densify_and_prune does (plain indexing: not a hot path)."""
+        params = self.parameter_list()
+        new = [nn.Parameter(p.data[mask].contiguous()) for p in params]
+        if optimizer is not None:
+            remap = {id(p): q for p, q in zip(params, new)}
+            for group in optimizer.param_groups:
+                group["params"] = [remap.get(id(p), p) for p in group["params"]]
+            for p, q in zip(params, new):
+                st = optimizer.state.pop(p, None)
+                if st:
+                    nst = dict(st)
+                    for key in ("exp_avg", "exp_avg_sq"):
+                        if key in nst:
+                            nst[key] = nst[key][mask].contiguous()
+                    optimizer.state[q] = nst
         (self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
-         self._opacity) = [nn.Parameter(p.data[mask].contiguous()) for p in self.parameter_list()]
+         self._opacity) = new
         self._reset_stats(self.get_num_points(), self._xyz.device)

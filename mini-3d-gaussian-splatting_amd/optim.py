@@ -330,6 +330,25 @@ class GaussianOptimizer:
         self.gaussians.reset_opacity()
 
     @torch.no_grad()
+    def prune_by_contribution(self, stats, threshold: float) -> dict:
+        """Drop every Gaussian whose largest blend weight over the views in
+        `stats` (ContributionStats.weight_max) is not above `threshold` (>= 0;
+        0 keeps exactly what contributed somewhere), the Adam moments of the
+        kept ones following them.  The criterion reads weight_max only, which
+        no summation order touches: every data-parallel rank and a single
+        process decide the same.  Returns {"n_before", "n_after"}."""
+        threshold = float(threshold)
+        if not threshold >= 0.0:
+            raise ValueError(f"the contribution threshold must be >= 0, got {threshold!r}")
+        g = self.gaussians
+        n = g.get_num_points()
+        if stats.n != n or stats.device != g._xyz.device:
+            raise ValueError(f"stats holds {stats.n} Gaussians on {stats.device}, the model {n} on {g._xyz.device}")
+        keep = stats.weight_max > threshold
+        g.prune_points(keep, self.optimizer)
+        return {"n_before": n, "n_after": g.get_num_points()}
+
+    @torch.no_grad()
     def cap_opacity(self, max_opacity: float = 0.01) -> None:
         """The 3DGS opacity reset: every opacity above max_opacity comes down to
         it -- _opacity.data = minimum(_opacity, logit(max_opacity)), the logit

@@ -349,6 +349,123 @@ def _accumulate_density(lib, cam: CameraParams, stats, n: int, vis, radii, grad_
     N.check(lib.gs_density_accumulate(C.byref(a), s), "gs_density_accumulate")
 
 
+class ContributionStats:
+    """How much each of `n` Gaussians on `device` contributed to the frames
+    rendered into it, with c_i(p) the blend's own weight of Gaussian i at
+    pixel p: weight_sum (fp32, the sum of c over every pixel of every view),
+    weight_max (fp32, the largest c anywhere: RadSplat's pruning score),
+    pixels (int64, how many pixels it reached with c > 0) and views (int32,
+    how many views saw it), each [n] and contiguous, starting at zero.
+
+    render(..., contribution_stats=stats) / rasterize(..., contribution_stats=stats)
+    add the view at the end of the forward; no backward is needed, and a
+    render under torch.no_grad() counts."""
+    __slots__ = ("n", "weight_sum", "weight_max", "pixels", "views")
+    _DTYPES = (("weight_sum", torch.float32), ("weight_max", torch.float32), ("pixels", torch.int64),
+               ("views", torch.int32))
+
+    def __init__(self, n: int, device):
+        self.n = int(n)
+        for name, dtype in self._DTYPES:
+            setattr(self, name, torch.zeros((self.n,), dtype=dtype, device=device))
+
+    @property
+    def device(self) -> torch.device:
+        return self.weight_sum.device
+
+    def reset(self) -> None:
+        for name, _ in self._DTYPES:
+            getattr(self, name).zero_()
+
+    def mean_weight(self) -> torch.Tensor:
+        """weight_sum / pixels, 0 where the Gaussian reached no pixel."""
+        hit = self.pixels > 0
+        return torch.where(hit, self.weight_sum / self.pixels.clamp_min(1).to(torch.float32),
+                           torch.zeros_like(self.weight_sum))
+
+    def all_reduce(self, dist) -> None:
+        """Combine the ranks' statistics (each rank rendered other views):
+        SUM, MAX, SUM, SUM.  dist: torch.distributed or a module like it."""
+        if not self.n:
+            return
+        dist.all_reduce(self.weight_sum, op=dist.ReduceOp.SUM)
+        dist.all_reduce(self.weight_max, op=dist.ReduceOp.MAX)
+        dist.all_reduce(self.pixels, op=dist.ReduceOp.SUM)
+        dist.all_reduce(self.views, op=dist.ReduceOp.SUM)
+
+
+def _check_contribution_stats(stats, n: int, dev) -> None:
+    if not isinstance(stats, ContributionStats):
+        raise TypeError(f"contribution_stats must be a ContributionStats, got {type(stats).__name__}")
+    if stats.n != n:
+        raise ValueError(f"contribution_stats holds {stats.n} Gaussians, the render {n}")
+    for name, dtype in ContributionStats._DTYPES:
+        t = getattr(stats, name)
+        if tuple(t.shape) != (n,) or t.dtype != dtype or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"contribution_stats.{name} must be a contiguous {dtype} [{n}] tensor on {dev}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+class _ContributionPass:
+    """What one render asked of the contribution pass (statistics to add the
+    view to, or None; the dominant-Gaussian maps or not) and, after the
+    forward, the maps."""
+    __slots__ = ("stats", "dominant", "dominant_id", "dominant_weight")
+
+    def __init__(self, stats, dominant: bool):
+        self.stats, self.dominant, self.dominant_id, self.dominant_weight = stats, bool(dominant), None, None
+
+
+def contribution_cell_batch(cells: int, entries: int) -> int:
+    """cell_batch's rule for the contribution pass's scratch: 16 B of partial
+    and 1 B of flag per (entry, cell)."""
+    per = 17 * max(int(entries), 1)
+    if cells <= _ALWAYS_ONE_BATCH or cells * per <= PARTIAL_BUDGET_BYTES:
+        return cells
+    return max(1, min(cells, PARTIAL_BUDGET_BYTES // per))
+
+
+def _contribution_pass(cam: CameraParams, fr: "_Frame", n: int, cp: _ContributionPass, dev) -> None:
+    """The contribution pass over a stage-path frame, at the end of its
+    forward: per cell batch one gs_blend_contributions into scratch partials
+    and flags of its own (the backward's are not touched) and, with
+    statistics, one gs_contrib_accumulate."""
+    H, W = int(cam.image_height), int(cam.image_width)
+    if cp.dominant:
+        cp.dominant_id = torch.empty((H, W), dtype=torch.int32, device=dev)
+        cp.dominant_weight = torch.empty((H, W), dtype=torch.float32, device=dev)
+    if fr.M == 0 or fr.T == 0:
+        if cp.dominant:
+            cp.dominant_id.fill_(-1)
+            cp.dominant_weight.zero_()
+        return
+    lib = N.load()
+    s = _stream()
+    T, Q = fr.T, cam.cells
+    G = contribution_cell_batch(Q, T)
+    partials = torch.empty((T * G, N.GS_CONTRIB_STRIDE), dtype=torch.float32, device=dev)
+    flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
+    ca = N.GsContribArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                         N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
+                         0 if fr.live_bits is None else fr.live_bits.shape[1], T, n, N.ptr(partials), N.ptr(flags),
+                         0, 0, N.ptr(cp.dominant_id), N.ptr(cp.dominant_weight))
+    st = cp.stats
+    if st is not None:
+        ga = N.GsContribGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(partials),
+                                   N.ptr(flags), G, 1, N.ptr(st.weight_sum), N.ptr(st.weight_max), N.ptr(st.pixels),
+                                   N.ptr(st.views))
+    for b, c0 in enumerate(range(0, Q, G)):
+        ca.cell_begin, ca.cell_count = c0, min(G, Q - c0)
+        flags.zero_()
+        StageTimer.mark("contrib_blend")
+        N.check(lib.gs_blend_contributions(C.byref(ca), s), "gs_blend_contributions")
+        if st is not None:
+            ga.partial_groups, ga.first_batch = ca.cell_count, (0 if b else 1)
+            StageTimer.mark("contrib_gather")
+            N.check(lib.gs_contrib_accumulate(C.byref(ga), s), "gs_contrib_accumulate")
+    StageTimer.mark("~end_contrib")
+
+
 class _Frame:
     """Intermediate device buffers of one forward, kept for the backward."""
     __slots__ = ("records", "rects", "vis", "pair_offset", "order", "ranges", "sorted_gauss", "pix_flags",
@@ -1284,7 +1401,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None):
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=True)
@@ -1292,6 +1409,8 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
         n, channels = int(features.shape[0]), int(features.shape[1])
         staged = _stage_features(features)
         feat_image = _feature_forward(cam, fr, staged, channels, n, xyz.device)
+        if contrib is not None:
+            _contribution_pass(cam, fr, n, contrib, xyz.device)
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
         ctx.feature_shape = (n, channels)
@@ -1336,7 +1455,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                d_features, None, None, None, None, g_view, None)
+                d_features, None, None, None, None, g_view, None, None)
 
 
 class RasterizeGaussians(torch.autograd.Function):
@@ -1345,7 +1464,9 @@ class RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None):
+        # contrib: a _ContributionPass: the frame is then the stage path's (the same bits) and the
+        # contribution pass runs at the end of this forward
         # density_stats: a DensityStats this frame's backward adds the view to (it needs the
         # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape)
         # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
@@ -1353,7 +1474,9 @@ class RasterizeGaussians(torch.autograd.Function):
         # reads the pose from `cam`, whose values are the same
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
-            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]))
+            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=contrib is not None)
+        if contrib is not None:
+            _contribution_pass(cam, fr, int(xyz.shape[0]), contrib, xyz.device)
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
         ctx.density = None if density_stats is None else (density_stats, radii)
@@ -1391,12 +1514,21 @@ class RasterizeGaussians(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                None, None, None, None, g_view, None)
+                None, None, None, None, g_view, None, None)
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
-              sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None, density_stats=None):
-    """density_stats: optional DensityStats of N Gaussians on their device: the
+              sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None, density_stats=None,
+              contribution_stats=None, dominant=False):
+    """contribution_stats: optional ContributionStats of N Gaussians on their
+    device (checked here, before any launch): the forward ends with the
+    contribution pass, which adds this view's per-Gaussian blend weights to
+    it (sum, max, pixel count, views).  dominant=True: two more outputs follow
+    (after the feature image, when there is one): the int32 [H, W] id of
+    each pixel's strongest contributor (-1: none) and its fp32 weight.
+    Neither needs a backward; both take the stage path, whose seven standard
+    outputs and gradients are the same bits.
+    density_stats: optional DensityStats of N Gaussians on their device: the
     backward of this render ends with one gs_density_accumulate that adds the
     view to it (checked here, before any launch; see DensityStats for what a
     missing or repeated backward means).  Without it the launches are the same.
@@ -1438,6 +1570,8 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
 
     if density_stats is not None:
         _check_density_stats(density_stats, n, xyz.device)
+    if contribution_stats is not None:
+        _check_contribution_stats(contribution_stats, n, xyz.device)
     xyz = prep("xyz", xyz, (3,))
     cov3d = prep("cov3d", cov3d, (3, 3))
     scaling = prep("scaling", scaling, (3,))
@@ -1478,21 +1612,25 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     opacity, _ = _rows(opacity, 1)
     # (the statistics ride behind `view`, only when given: without them the calls are the ones they were)
     stats = () if density_stats is None else (density_stats,)
+    cp = _ContributionPass(contribution_stats, dominant) if (contribution_stats is not None or dominant) else None
+    if cp is not None:
+        stats = (density_stats, cp)
     if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
         if stats:
             stats = (None,) + stats
-        if features is not None:
-            return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
-                                                   cam, bool(opacity_is_logit), sh_degree, grad_dest, *stats)
-        return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                        bool(opacity_is_logit), sh_degree, grad_dest, *stats)
-    if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
-        raise ValueError(f"view must be a floating-point [3,4] or [4,4] tensor, got {view.dtype} {tuple(view.shape)}")
-    # (differentiable, as the reference's .to(device): the gradient returns to
-    # the caller's device and dtype)
-    view = view.to(device=xyz.device, dtype=torch.float32)
+    else:
+        if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
+            raise ValueError(f"view must be a floating-point [3,4] or [4,4] tensor, got {view.dtype} "
+                             f"{tuple(view.shape)}")
+        # (differentiable, as the reference's .to(device): the gradient returns to
+        # the caller's device and dtype)
+        stats = (view.to(device=xyz.device, dtype=torch.float32),) + stats
     if features is not None:
-        return RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
-                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, view, *stats)
-    return RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                    bool(opacity_is_logit), sh_degree, grad_dest, view, *stats)
+        outs = RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
+                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, *stats)
+    else:
+        outs = RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
+                                        bool(opacity_is_logit), sh_degree, grad_dest, *stats)
+    if cp is not None and cp.dominant:
+        outs = tuple(outs) + (cp.dominant_id, cp.dominant_weight)
+    return outs

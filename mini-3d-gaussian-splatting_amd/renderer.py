@@ -45,7 +45,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _native as N
-from .rasterizer import CameraParams, DensityStats, check_screen_filter, rasterize
+from .rasterizer import CameraParams, ContributionStats, DensityStats, check_screen_filter, rasterize
 
 
 @dataclass
@@ -150,8 +150,24 @@ class GaussianRenderer:
 
     def render(self, camera, gaussians, settings: RenderSettings,
                features: Optional[torch.Tensor] = None,
-               density_stats: Optional[DensityStats] = None) -> Dict[str, torch.Tensor]:
-        """density_stats: optional DensityStats of the model's size on its
+               density_stats: Optional[DensityStats] = None,
+               contribution_stats: Optional[ContributionStats] = None,
+               dominant: bool = False) -> Dict[str, torch.Tensor]:
+        """contribution_stats: optional ContributionStats of the model's size
+        on its device.  The forward of this render then ends with the
+        contribution pass: per Gaussian, the sum and the maximum over the
+        image of its blend weight c_i(p) -- the weights the colour pass
+        itself used -- the number of pixels with c_i(p) > 0 and one more view
+        for every visible Gaussian are added to it.  No backward is needed: a
+        render under torch.no_grad() counts.  Mismatches are a ValueError
+        before anything is launched.
+        dominant: the result also holds "dominant_gaussian" (int32 [H, W],
+        the index of each pixel's strongest contributor, the first in depth
+        order among equals, -1 where nothing contributes) and
+        "dominant_weight" (fp32 [H, W], its c).
+        With either, the frame takes the stage path, as with features=: the
+        seven standard outputs and their gradients are the same bits.
+        density_stats: optional DensityStats of the model's size on its
         device.  The backward of this render then ends with one launch that
         adds the view to them: per visible Gaussian the NDC-unit norm of
         dL/d(viewspace_points) -- the blend's part, which never surfaces as a
@@ -230,6 +246,10 @@ class GaussianRenderer:
             extra["features"] = features
         if density_stats is not None:
             extra["density_stats"] = density_stats
+        if contribution_stats is not None:
+            extra["contribution_stats"] = contribution_stats
+        if dominant:
+            extra["dominant"] = True
         image, alpha, depth, means2d, conics, radii, vis, *feature_image = rasterize(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
             sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **extra)
@@ -250,6 +270,9 @@ class GaussianRenderer:
             "radii": radii,
             "conics": conics,
         }
+        if dominant:
+            out["dominant_gaussian"], out["dominant_weight"] = feature_image[-2:]
+            feature_image = feature_image[:-2]
         if feature_image:
             out["features"] = feature_image[0]
         return out

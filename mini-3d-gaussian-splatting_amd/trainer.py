@@ -50,6 +50,7 @@ class GaussianTrainer:
         self._reducer_n = -1
         self._perm: Optional[np.ndarray] = None
         self.last_densify: Optional[dict] = None  # the counts of the latest densification
+        self.last_compact: Optional[dict] = None  # the counts of the latest contribution pruning
 
     # -- setup (trainer.py:32-44) ------------------------------------------
     def _device(self) -> torch.device:
@@ -142,7 +143,38 @@ class GaussianTrainer:
         if (c.opacity_reset_interval > 0 and self.iteration % c.opacity_reset_interval == 0
                 and self.iteration <= c.densify_until_iter):
             opt.cap_opacity()
+        if c.contribution_prune_iterations and self.iteration in c.contribution_prune_iterations:
+            self.last_compact = self.compact()
         return {"loss": total.detach(), "l1": l1, "dssim": dssim}
+
+    @torch.no_grad()
+    def compact(self, threshold: Optional[float] = None, cameras=None) -> Dict[str, int]:
+        """Contribution pruning: render `cameras` (default: the training
+        cameras) with the training render settings into
+        gaussians.contribution_stats, without gradients, and drop every
+        Gaussian whose largest blend weight over all of them is not above
+        `threshold` (default: config.contribution_prune_threshold); Adam
+        moments follow the kept ones.  Data parallel: each rank renders
+        cameras[rank::world], the statistics are all-reduced, and every rank
+        takes the same decision.  Returns {"n_before", "n_after"}."""
+        g, c = self.gaussians, self.config
+        if threshold is None:
+            threshold = c.contribution_prune_threshold
+        if not float(threshold) >= 0.0:
+            raise ValueError(f"the contribution threshold must be >= 0, got {threshold!r}")
+        cams = list(self.dataset.get_train_cameras() if cameras is None else cameras)
+        if self._dist is not None:
+            cams = cams[self._dist.get_rank()::self._dist.get_world_size()]
+        stats = g.contribution_stats
+        stats.reset()
+        for cam in cams:
+            self.renderer.render(cam, g, self._settings(cam), contribution_stats=stats)
+        if self._dist is not None:
+            stats.all_reduce(self._dist)
+        info = self.optimizer.prune_by_contribution(stats, threshold)
+        self._reducer = None  # (the bucket was sized for the old N)
+        g.contribution_stats.reset()
+        return info
 
     def close(self) -> None:
         """Tear down the data-parallel transport: the native RCCL communicators
