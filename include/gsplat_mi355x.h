@@ -817,6 +817,109 @@ size_t gs_densify_workspace_bytes(int32_t n);
 gs_status gs_densify_count(const gs_densify_args *a, gs_stream_t stream);
 gs_status gs_densify_emit(const gs_densify_args *a, gs_stream_t stream);
 
+/* ---- MCMC density control (3DGS-MCMC, Kheradmand et al. 2024) -------------
+ * The other family of density control: nothing is pruned and no gradient
+ * threshold decides.  Dead Gaussians (opacity <= min_opacity) are moved onto
+ * live ones drawn with probability proportional to their opacity, so that the
+ * rendered image is preserved; new rows are added the same way up to a fixed
+ * cap; and every iteration the positions get opacity-gated noise.  (Not in
+ * the reference.)  All four entry points: one thread per item, no allocation,
+ * no floating-point atomics; a NULL required pointer, a negative size or a
+ * non-finite scalar is GS_ERR_INVALID_ARG before any HIP call; n == 0 or zero
+ * samples is GS_OK with nothing launched.
+ *
+ * gs_mcmc_sample: weighted sampling with replacement, exact and reproducible.
+ * cdf[i] is the inclusive prefix sum of non-negative integer weights
+ * (total = cdf[n-1], read on the device).  With mix64 the splitmix64 finaliser
+ * (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31), sample j is
+ *   h = mix64(seed ^ mix64(j)),  r = (h * total) >> 64,
+ *   idx[j] = the smallest i with cdf[i] > r,   counts[idx[j]] += 1 (integer atomic)
+ * so a row of weight 0 is never drawn.  counts is zeroed by the caller.
+ * total == 0: GS_OK, nothing written (there is nothing to draw from). */
+typedef struct gs_mcmc_sample_args {
+  int32_t n;            /* rows of cdf and counts */
+  int32_t num_samples;
+  const int64_t *cdf;   /* [n] inclusive prefix sums, non-decreasing, cdf[n-1] < 2^63 */
+  uint64_t seed;
+  int32_t *idx;         /* [num_samples] out */
+  int32_t *counts;      /* [n] in/out: += the times each row was drawn */
+} gs_mcmc_sample_args;
+gs_status gs_mcmc_sample(const gs_mcmc_sample_args *a, gs_stream_t stream);
+
+/* gs_mcmc_relocate: the relocation (paper Eq. 9), in place, two launches.
+ * Launch 1, per sample j with s = idx[j], in double from the fp32 inputs:
+ *   R = min(counts[s] + 1, 51)
+ *   o = min(sigmoid(opacity[s]), 1 - 2^-24)
+ *   x = 1 - (1 - o)^(1/R)
+ *   D = sum_{i=1..R} sum_{k=0..i-1} C(i-1, k) (-1)^k x^(k+1) / sqrt(k+1)
+ *   opacity' = logit(clamp(x, min_opacity, 1 - 2^-24))
+ *   scaling'[k] = scaling[s][k] + log(o / D)      (scaling[s][k] if D is not a positive finite number)
+ * each rounded once to fp32 into workspace[j].  R == 1: x = o, D = o, the
+ * scale unchanged.  Launch 2, per sample j: row dst[j] gets xyz, features_dc,
+ * features_rest and rotation of row s bit for bit and opacity', scaling';
+ * row s gets opacity', scaling' too; the rows s and dst[j] of every array
+ * given in adam_m / adam_v become zero (NULL members are skipped).
+ * Preconditions (the caller's; they make launch 2 free of races): the dst
+ * rows are distinct, and no dst row is also sampled -- dead rows have weight
+ * 0, appended rows lie past n.  idx[j] outside [0, n) or dst[j] outside
+ * [0, rows) skips the sample.  min_opacity outside (0, 1): GS_ERR_INVALID_ARG. */
+typedef struct gs_mcmc_relocate_args {
+  int32_t n;                 /* rows that can be sampled: counts is [n], idx[j] < n */
+  int32_t rows;              /* rows of params and the moments (>= n): dst[j] < rows */
+  int32_t rest_floats;
+  int32_t num_samples;
+  gs_model_arrays params;    /* in place */
+  gs_model_arrays adam_m, adam_v; /* in place; NULL members: not touched */
+  const int32_t *idx;        /* [num_samples] gs_mcmc_sample's */
+  const int32_t *counts;     /* [n] gs_mcmc_sample's */
+  const int32_t *dst;        /* [num_samples] the rows that receive the copies */
+  float min_opacity;
+  void *workspace;           /* gs_mcmc_relocate_workspace_bytes(num_samples), 16-byte aligned */
+  size_t workspace_bytes;
+} gs_mcmc_relocate_args;
+size_t gs_mcmc_relocate_workspace_bytes(int32_t num_samples);
+gs_status gs_mcmc_relocate(const gs_mcmc_relocate_args *a, gs_stream_t stream);
+
+/* gs_mcmc_noise: the per-iteration position noise, one streaming launch
+ * (44 B read, 12 B written per Gaussian).  Per Gaussian i, in fp32:
+ *   q = rotation[i] / max(|rotation[i]|, 1e-12),  Sigma = R(q) diag(exp(scaling[i])^2) R(q)^T
+ *   o = sigmoid(opacity[i]),  gate = 1 / (1 + expf(-gate_steepness * (gate_midpoint - o)))
+ *   eps[k] = the counter-based standard normal of (seed, i, k), k < 3 (the clone jitter's)
+ *   xyz[i] += Sigma eps * (gate * scale)
+ * scale = noise_lr * the xyz learning rate, formed by the caller.  Only xyz
+ * is written.  scale == 0: GS_OK, nothing launched.  rotation is read as one
+ * 16-byte vector per row and must be 16-byte aligned. */
+typedef struct gs_mcmc_noise_args {
+  int32_t n;
+  float *xyz;            /* [n,3] in place */
+  const float *scaling;  /* [n,3] log */
+  const float *rotation; /* [n,4] */
+  const float *opacity;  /* [n] logit */
+  uint64_t seed;
+  float scale;
+  float gate_steepness;  /* 100 */
+  float gate_midpoint;   /* 0.005 (1 - the paper's 0.995) */
+} gs_mcmc_noise_args;
+gs_status gs_mcmc_noise(const gs_mcmc_noise_args *a, gs_stream_t stream);
+
+/* gs_mcmc_regularize: the gradients of
+ *   lambda_opacity * mean(sigmoid(opacity)) + lambda_scale * mean(exp(scaling))
+ * added to existing gradient buffers, with o = sigmoid(opacity[i]):
+ *   d_opacity[i]    += (lambda_opacity / n) * o * (1 - o)
+ *   d_scaling[i][k] += (lambda_scale / (3 n)) * exp(scaling[i][k])
+ * (the two factors formed in double and rounded to fp32 once).  A NULL
+ * gradient pointer skips that term; both NULL: nothing launched. */
+typedef struct gs_mcmc_regularize_args {
+  int32_t n;
+  const float *opacity;  /* [n] logit */
+  const float *scaling;  /* [n,3] log */
+  float *d_opacity;      /* [n], or NULL */
+  float *d_scaling;      /* [n,3], or NULL */
+  float lambda_opacity, lambda_scale;
+} gs_mcmc_regularize_args;
+gs_status gs_mcmc_regularize(const gs_mcmc_regularize_args *a, gs_stream_t stream);
+
 /* ---- Frame entry points: the stages above in one call per direction -------
  * gs_render_forward runs what GaussianRenderer.render does (renderer.py:31-114)
  * -- projection + culling, depth sort, binning, tile sort, ranges, blend --

@@ -15,10 +15,11 @@ from .dataset import CameraDataset, NeRFSyntheticDataset, COLMAPDataset, load_da
 from .trainer import GaussianTrainer  # noqa: F401
 from .graph_step import GraphedStep  # noqa: F401
 from .pose import CameraPose, se3_exp  # noqa: F401
-from . import _native, synthetic, distributed, optim, loss, dataset, trainer, graph_step, pose  # noqa: F401
+from .mcmc import mcmc_sample, mcmc_relocate, mcmc_noise, mcmc_regularize  # noqa: F401
+from . import _native, synthetic, distributed, optim, loss, dataset, trainer, graph_step, pose, mcmc  # noqa: F401
 
 __all__ = ["GaussianRenderer", "RenderSettings", "GaussianModel", "Camera", "CameraUtils",
            "CameraParams", "rasterize", "camera_params", "SSIMLoss", "GaussianLoss", "photometric_loss",
            "TrainingConfig", "ConfigManager", "CameraDataset", "NeRFSyntheticDataset", "COLMAPDataset",
            "load_dataset", "GaussianTrainer", "GraphedStep", "CameraPose", "se3_exp", "DensityStats",
-           "ContributionStats"]
+           "ContributionStats", "mcmc_sample", "mcmc_relocate", "mcmc_noise", "mcmc_regularize"]

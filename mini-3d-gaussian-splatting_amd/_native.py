@@ -267,6 +267,41 @@ class GsDensityStatsArgs(C.Structure):
     ]
 
 
+class GsMcmcSampleArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("num_samples", C.c_int32), ("cdf", _vp), ("seed", C.c_uint64), ("idx", _vp),
+                ("counts", _vp)]
+
+
+class GsMcmcRelocateArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("rows", C.c_int32), ("rest_floats", C.c_int32), ("num_samples", C.c_int32),
+        ("params", GsModelArrays), ("adam_m", GsModelArrays), ("adam_v", GsModelArrays), ("idx", _vp),
+        ("counts", _vp), ("dst", _vp), ("min_opacity", C.c_float), ("workspace", _vp),
+        ("workspace_bytes", C.c_size_t),
+    ]
+
+
+GS_MCMC_GATE_STEEPNESS, GS_MCMC_GATE_MIDPOINT = 100.0, 0.005  # gs_mcmc_noise_args' gate (3DGS-MCMC's)
+
+
+class GsMcmcNoiseArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("xyz", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp),
+                ("seed", C.c_uint64), ("scale", C.c_float), ("gate_steepness", C.c_float),
+                ("gate_midpoint", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        for k, (name, default) in enumerate((("gate_steepness", GS_MCMC_GATE_STEEPNESS),
+                                             ("gate_midpoint", GS_MCMC_GATE_MIDPOINT)), start=7):
+            if len(args) <= k:  # (not given by position)
+                kw.setdefault(name, default)
+        super().__init__(*args, **kw)
+
+
+class GsMcmcRegularizeArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("opacity", _vp), ("scaling", _vp), ("d_opacity", _vp), ("d_scaling", _vp),
+                ("lambda_opacity", C.c_float), ("lambda_scale", C.c_float)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -278,6 +313,7 @@ EXPORTS = (
     "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit", "gs_density_accumulate",
     "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
     "gs_blend_contributions", "gs_contrib_accumulate",
+    "gs_mcmc_sample", "gs_mcmc_relocate_workspace_bytes", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize",
 )
 
 _lib = None
@@ -344,11 +380,18 @@ def _declare(lib):
     lib.gs_gather_feature_partials.argtypes = [P(GsFeatureGatherArgs), _vp]
     lib.gs_blend_contributions.argtypes = [P(GsContribArgs), _vp]
     lib.gs_contrib_accumulate.argtypes = [P(GsContribGatherArgs), _vp]
+    lib.gs_mcmc_sample.argtypes = [P(GsMcmcSampleArgs), _vp]
+    lib.gs_mcmc_relocate_workspace_bytes.argtypes = [C.c_int32]
+    lib.gs_mcmc_relocate_workspace_bytes.restype = C.c_size_t
+    lib.gs_mcmc_relocate.argtypes = [P(GsMcmcRelocateArgs), _vp]
+    lib.gs_mcmc_noise.argtypes = [P(GsMcmcNoiseArgs), _vp]
+    lib.gs_mcmc_regularize.argtypes = [P(GsMcmcRegularizeArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
               "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
-              "gs_blend_contributions", "gs_contrib_accumulate"):
+              "gs_blend_contributions", "gs_contrib_accumulate", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
+              "gs_mcmc_regularize"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -56,7 +56,7 @@ class TrainingConfig:
     # what densification reads: "xyz_grad", |dL/dxyz| of the iteration's one view, or "screen", the
     # 3DGS criterion: the NDC-unit gradient norm at the projected centre, averaged over the views that
     # saw the Gaussian since the last densification (the quantity densify_grad_threshold is the 3DGS
-    # value of)
+    # value of); or "mcmc", the 3DGS-MCMC family (the mcmc_* fields below)
     densify_criterion: str = "xyz_grad"
     prune_screen_radius: float = 0.0   # "screen": also prune Gaussians whose largest screen radius (px) exceeded it; 0 = off
     # cap opacities at 0.01 every this many iterations while densifying (0 = never); a Gaussian the
@@ -72,6 +72,17 @@ class TrainingConfig:
     # is not above the threshold are dropped (0.01: RadSplat's default); () = never
     contribution_prune_iterations: tuple = ()
     contribution_prune_threshold: float = 0.01
+    # densify_criterion "mcmc" (3DGS-MCMC, on the densify_from_iter / _until_iter / _interval schedule):
+    # nothing is pruned; at a refinement the Gaussians with opacity <= mcmc_min_opacity are relocated onto
+    # live ones and N grows by mcmc_grow_factor up to mcmc_cap_max, after which no tensor is reallocated;
+    # every iteration the positions get opacity-gated noise of mcmc_noise_lr * the position learning rate,
+    # and the loss gains mcmc_opacity_reg * mean(opacity) + mcmc_scale_reg * mean(scale)
+    mcmc_cap_max: int = 1_000_000
+    mcmc_min_opacity: float = 0.005
+    mcmc_noise_lr: float = 5e5
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
+    mcmc_grow_factor: float = 1.05
 
     def __post_init__(self):
         # (a YAML file holds the iterations as a list)
@@ -91,9 +102,23 @@ class TrainingConfig:
         if isinstance(its, (str, bytes)) or not all(isinstance(i, int) and not isinstance(i, bool) and i > 0
                                                     for i in its):
             raise ValueError(f"contribution_prune_iterations must hold positive iteration numbers, got {its!r}")
+        if self.densify_criterion == "mcmc":
+            if isinstance(self.mcmc_cap_max, bool) or not isinstance(self.mcmc_cap_max, int) or self.mcmc_cap_max < 1:
+                raise ValueError(f"mcmc_cap_max must be an integer >= 1, got {self.mcmc_cap_max!r}")
+            for name in ("mcmc_noise_lr", "mcmc_opacity_reg", "mcmc_scale_reg"):
+                v = float(getattr(self, name))
+                if not (v >= 0.0 and v != float("inf")):
+                    raise ValueError(f"{name} must be finite and >= 0, got {getattr(self, name)!r}")
+            if not (float(self.mcmc_grow_factor) >= 1.0 and float(self.mcmc_grow_factor) != float("inf")):
+                raise ValueError(f"mcmc_grow_factor must be finite and >= 1, got {self.mcmc_grow_factor!r}")
+            if not 0.0 < float(self.mcmc_min_opacity) < 1.0:
+                raise ValueError(f"mcmc_min_opacity must lie in (0, 1), got {self.mcmc_min_opacity!r}")
+            if self.opacity_reset_interval > 0 or self.prune_screen_radius > 0:
+                raise ValueError("opacity_reset_interval and prune_screen_radius belong to the split / clone / prune "
+                                 "criteria, not to densify_criterion 'mcmc'")
 
 
-DENSIFY_CRITERIA = ("xyz_grad", "screen")
+DENSIFY_CRITERIA = ("xyz_grad", "screen", "mcmc")
 
 
 def _need_yaml():

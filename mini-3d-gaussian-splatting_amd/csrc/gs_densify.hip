@@ -16,6 +16,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "gs_device.h"
 #include "gs_internal.h"
 #include "gsplat_mi355x.h"
 
@@ -62,42 +63,6 @@ __device__ Cls classify(const gs_densify_args &a, int i) {
   c.split = split && child_alive;
   c.clone = clone && alive && !big;
   return c;
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// standard normal from (seed, i, k): Box-Muller on two 24-bit uniforms
-__device__ float normal_of(uint64_t seed, uint32_t i, uint32_t k) {
-  const uint64_t h = mix64(seed ^ mix64((uint64_t)i * 4u + k));
-  const float u1 = (float)((h >> 40) + 1ull) * 0x1p-24f;  // (0, 1]
-  const float u2 = (float)((h >> 16) & 0xFFFFFFull) * 0x1p-24f;
-  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
-
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t *s_tmp, uint32_t *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) s_tmp[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < kB / 64; ++w) {
-    const uint32_t x = s_tmp[w];
-    base += (w < wave) ? x : 0u;
-    tot += x;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
 }
 
 __global__ __launch_bounds__(kB) void k_densify_count(gs_densify_args a, uint32_t *part) {

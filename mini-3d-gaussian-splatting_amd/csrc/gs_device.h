@@ -1,9 +1,10 @@
 // gs_device.h -- what more than one stage of the render path uses: the block
 // geometry, the block scans, the DPP lane sums, the under-aligned vector
-// types, the one Adam update, and the host-side camera check.  Everything is
-// in an anonymous namespace (each .hip file is its own translation unit and
-// code object); a helper with a single user lives in that user's file.
-// Not part of the C ABI.  Wave size is 64 everywhere.
+// types, the counter-based normals, the one Adam update, and the host-side
+// camera check.  Everything is in an anonymous namespace (each .hip file is
+// its own translation unit and code object); a helper with a single user
+// lives in that user's file.  Not part of the C ABI.  Wave size is 64
+// everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,6 +96,24 @@ __device__ __forceinline__ uint3 block_exscan3(uint3 v, uint32_t (*s_tmp)[kBlock
 // touches of a packed tile rectangle (k_project_fwd's rects; empty: tx0 > tx1)
 __device__ __forceinline__ uint32_t rect_touches(int tx0, int tx1, int ty0, int ty1) {
   return (tx1 >= tx0 && ty1 >= ty0) ? (uint32_t)((tx1 - tx0 + 1) * (ty1 - ty0 + 1)) : 0u;
+}
+
+// ------------------------------------------------- counter-based noise ----
+// splitmix64's finaliser: the hash every seeded draw here goes through
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// standard normal from (seed, i, k): Box-Muller on two 24-bit uniforms (the
+// clone jitter of gs_densify.hip and the position noise of gs_mcmc.hip; its
+// bits are pinned by tests/test_densify.py)
+__device__ float normal_of(uint64_t seed, uint32_t i, uint32_t k) {
+  const uint64_t h = mix64(seed ^ mix64((uint64_t)i * 4u + k));
+  const float u1 = (float)((h >> 40) + 1ull) * 0x1p-24f;  // (0, 1]
+  const float u2 = (float)((h >> 16) & 0xFFFFFFull) * 0x1p-24f;
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
 }
 
 // ------------------------------------------------------------ DPP sums ----

@@ -297,6 +297,80 @@ class GaussianModel(nn.Module):
         self._reset_stats(n_out, dev)
         return {"kept": kept, "split": nsplit, "cloned": ncl, "n": n_out}
 
+    # -- MCMC density control (3DGS-MCMC; include/gsplat_mi355x.h) ---------------
+    @torch.no_grad()
+    def relocate_and_grow(self, cap_max: int, min_opacity: float, seed: int,
+                          optimizer: Optional[torch.optim.Optimizer] = None, grow_factor: float = 1.05) -> dict:
+        """One 3DGS-MCMC refinement.  Every dead Gaussian (sigmoid(opacity) <=
+        min_opacity) becomes a copy of a live one drawn with probability
+        proportional to its opacity (seed), the copies and their source sharing
+        the source's opacity and scale so that the render is preserved
+        (gs_mcmc_relocate); then min(cap_max, int(grow_factor * n)) - n rows
+        are appended the same way (seed + 1).  Nothing is pruned.  With
+        `optimizer`, the Adam moments of every source and destination row
+        start over from zero and the step counts stay.  Once n has reached
+        cap_max nothing is reallocated: parameters and moments keep their
+        addresses.  (A copy whose opacity the relocation clamps to min_opacity
+        sits on the dead line and may be relocated again next time, as in the
+        paper's implementation.)  Returns {"n_before", "relocated", "added", "n"}."""
+        from . import mcmc
+        params = self.parameter_list()
+        n, dev = self.get_num_points(), self._xyz.device
+        cap_max, min_opacity, seed = int(cap_max), float(min_opacity), int(seed)
+        if cap_max < 1 or not grow_factor >= 1.0 or not 0.0 < min_opacity < 1.0:
+            raise ValueError("relocate_and_grow needs cap_max >= 1, grow_factor >= 1 and min_opacity in (0, 1)")
+        for p in params:
+            if not (p.is_cuda and p.is_contiguous()):
+                raise RuntimeError("relocate_and_grow needs contiguous parameters on a HIP device")
+        info = {"n_before": n, "relocated": 0, "added": 0, "n": n}
+        if n == 0:
+            return info
+        states = [optimizer.state.get(p, {}) if optimizer is not None else {} for p in params]
+        dead = torch.sigmoid(self._opacity.detach()[:, 0]) <= min_opacity
+        n_dead = int(dead.sum())  # (the refinement's one host read)
+        if 0 < n_dead < n:
+            cdf = mcmc.opacity_cdf(self._opacity, min_opacity)
+            idx, counts = mcmc.mcmc_sample(cdf, n_dead, seed)
+            dst = torch.nonzero(dead)[:, 0].to(torch.int32)  # (index order)
+            mcmc.mcmc_relocate([p.data for p in params], idx, counts, dst, min_opacity,
+                               [st.get("exp_avg") for st in states], [st.get("exp_avg_sq") for st in states])
+            info["relocated"] = n_dead
+        n_new = min(cap_max, int(grow_factor * n)) - n
+        if n_new <= 0 or n_dead == n:
+            return info
+
+        def grown(t):
+            out = torch.zeros((n + n_new,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            out[:n].copy_(t)
+            return out
+
+        outs = [grown(p.data) for p in params]
+        m_out = [grown(st["exp_avg"]) if "exp_avg" in st else None for st in states]
+        v_out = [grown(st["exp_avg_sq"]) if "exp_avg_sq" in st else None for st in states]
+        cdf = mcmc.opacity_cdf(outs[5][:n], min_opacity)  # (after the relocation)
+        idx, counts = mcmc.mcmc_sample(cdf, n_new, seed + 1)
+        dst = torch.arange(n, n + n_new, dtype=torch.int32, device=dev)
+        mcmc.mcmc_relocate(outs, idx, counts, dst, min_opacity, m_out, v_out)
+        new = [nn.Parameter(o) for o in outs]
+        if optimizer is not None:
+            remap = {id(p): q for p, q in zip(params, new)}
+            for group in optimizer.param_groups:
+                group["params"] = [remap.get(id(p), p) for p in group["params"]]
+            for p, q, st, m, v in zip(params, new, states, m_out, v_out):
+                optimizer.state.pop(p, None)
+                if st:
+                    nst = dict(st)
+                    if m is not None:
+                        nst["exp_avg"] = m
+                    if v is not None:
+                        nst["exp_avg_sq"] = v
+                    optimizer.state[q] = nst
+        (self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+         self._opacity) = new
+        self._reset_stats(n + n_new, dev)
+        info["added"], info["n"] = n_new, n + n_new
+        return info
+
     def density_and_split(self, grad_threshold: float, scene_extent: float) -> None:
         """gaussian_model.py:131-157 (split only, no opacity prune)."""
         self.densify_and_prune(grad_threshold, scene_extent, split=True, clone=False, prune=False)

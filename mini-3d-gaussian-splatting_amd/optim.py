@@ -326,6 +326,35 @@ class GaussianOptimizer:
             return info
         return None
 
+    # -- densify_criterion "mcmc" (3DGS-MCMC) -------------------------------------
+    def mcmc_regularize(self) -> None:
+        """Add the gradients of mcmc_opacity_reg * mean(opacity) + mcmc_scale_reg *
+        mean(scale) to _opacity.grad and _scaling.grad (one launch, before the
+        Adam step; a parameter without a gradient is skipped)."""
+        from . import mcmc
+        g, c = self.gaussians, self.config
+        mcmc.mcmc_regularize(g._opacity.data, g._scaling.data, g._opacity.grad, g._scaling.grad,
+                             c.mcmc_opacity_reg, c.mcmc_scale_reg)
+
+    def relocate_and_grow(self, iteration: int):
+        """On a refinement iteration (the densification schedule),
+        GaussianModel.relocate_and_grow seeded by the iteration; else None."""
+        if not self.density_controller.should_densify(iteration):
+            return None
+        c = self.config
+        return self.gaussians.relocate_and_grow(c.mcmc_cap_max, c.mcmc_min_opacity, 0x3C3C0000 + 2 * iteration,
+                                                optimizer=self.optimizer, grow_factor=c.mcmc_grow_factor)
+
+    def mcmc_noise(self, iteration: int) -> None:
+        """The iteration's position noise (one launch, after the Adam step and
+        the refinement): mcmc_noise_lr * the xyz group's current learning
+        rate, seeded by the iteration."""
+        from . import mcmc
+        g = self.gaussians
+        scale = float(self.config.mcmc_noise_lr) * float(self.optimizer.param_groups[0]["lr"])
+        mcmc.mcmc_noise(g._xyz.data, g._scaling.data, g._rotation.data, g._opacity.data, scale,
+                        0x401E0000 + iteration)
+
     def reset_opacity(self) -> None:
         self.gaussians.reset_opacity()
 

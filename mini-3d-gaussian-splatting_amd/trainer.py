@@ -9,7 +9,9 @@ densify_until_iter] (optimizer.py:34-141) -- on |dL/dxyz| of the iteration's
 view, or with densify_criterion = "screen" on the 3DGS statistics every
 render's backward adds to gaussians.density_stats (then also
 prune_screen_radius and, every opacity_reset_interval iterations, the 3DGS
-opacity reset).  Nothing in a step reads a value
+opacity reset), or with densify_criterion = "mcmc" the 3DGS-MCMC family
+(_mcmc_update: regularisers, relocation and capped growth in place of split /
+clone / prune, position noise every iteration).  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.
 
 Data parallel: with torch.distributed initialised,
@@ -130,6 +132,9 @@ class GaussianTrainer:
         total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
         total.backward()
         opt.update_learning_rate(self.iteration)
+        if c.densify_criterion == "mcmc":
+            self._mcmc_update()
+            return {"loss": total.detach(), "l1": l1, "dssim": dssim}
         if self._dist is not None:
             # mean all-reduce, then Adam; pipelined per Gaussian range when the
             # backward handed its rows over in ranges (GS_ALLREDUCE_CHUNKS)
@@ -146,6 +151,28 @@ class GaussianTrainer:
         if c.contribution_prune_iterations and self.iteration in c.contribution_prune_iterations:
             self.last_compact = self.compact()
         return {"loss": total.detach(), "l1": l1, "dssim": dssim}
+
+    def _mcmc_update(self) -> None:
+        """The rest of a step with densify_criterion "mcmc", after the backward:
+        [gradient mean], the regularisers' gradients, Adam, on a refinement
+        iteration relocate_and_grow, and the position noise.  Every seed is
+        the iteration's, and the regulariser is added after the mean (the
+        same bits on every rank), so replicas and resumed runs stay
+        bit-identical.  The bucket is dropped only when tensors were replaced:
+        once N is at mcmc_cap_max nothing moves again."""
+        opt, c = self.optimizer, self.config
+        if self._dist is not None:
+            self._reducer.all_reduce_mean()
+        opt.mcmc_regularize()
+        opt.step()
+        info = opt.relocate_and_grow(self.iteration)
+        if info is not None:
+            self.last_densify = info
+            if info["added"]:
+                self._reducer = None
+        opt.mcmc_noise(self.iteration)
+        if c.contribution_prune_iterations and self.iteration in c.contribution_prune_iterations:
+            self.last_compact = self.compact()
 
     @torch.no_grad()
     def compact(self, threshold: Optional[float] = None, cameras=None) -> Dict[str, int]:
