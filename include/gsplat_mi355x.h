@@ -564,6 +564,100 @@ typedef struct gs_contrib_gather_args {
 } gs_contrib_gather_args;
 gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t stream);
 
+/* ---- Depth distortion and median depth through the blend -------------------
+ * How spread out along the ray a pixel's contributors are, and the depth of
+ * the one surface at which its opacity crosses one half: a fourth replay of
+ * the colour forward (ranges / sorted_gauss / records / cell_neval /
+ * live_bits, as the feature kernels; any tile_size; live_bits NULL: every
+ * entry of a cell's evaluated prefix), one 64-lane workgroup per (tile, 8x8
+ * cell), lane = pixel.  With c_i the forward's own contribution weight of
+ * entry i of the pixel's tile list (c = (1 - A) alpha, A = A + c; +0 for a
+ * skipped pair, a terminated pixel, or a lane outside the tile or image),
+ * z_i the camera-space depth in the entry's record (float 9) and m_i its
+ * mapped depth,
+ *   A_i = sum_{j<=i} c_j,   S_i = sum_{j<=i} c_j m_j   (A_0 = S_0 = 0)
+ *   distortion(p) = 2 sum_i c_i (m_i A_{i-1} - S_{i-1})
+ * The lists are sorted by the bits of z and both depth maps are monotone, so
+ * this is the Mip-NeRF 360 / 2DGS distortion sum_i sum_j c_i c_j |m_i - m_j|;
+ * a pixel with fewer than two contributors has 0.  The sum does not change
+ * under a shift common to all m, and the kernels use one: every m is formed
+ * directly as a difference to the pixel's first contributor f (the first
+ * entry with c > 0, a decision of the replay, the same in both directions),
+ *   linear  (near = far = 0):    m_i = z_i - z_f
+ *   inverse (0 < near < far):    m_i = kappa (z_i - z_f) / (z_i z_f),  kappa = far near / (far - near)
+ * the latter 2DGS's NDC depth far (z - near) / ((far - near) z) minus its
+ * value at z_f.  Formed from unshifted fp32 values, m_i A - S loses a scene at
+ * depth 2000 with a spread of 0.5 to cancellation, and the inverse map puts
+ * everything into the last ulps below 1; as differences every term is
+ * bounded by the pixel's own depth spread.
+ * Median: the first entry with c_i > 0 after whose addition the fp32 running
+ * A_i >= 0.5; if A never reaches 0.5, the last entry with c_i > 0; if there
+ * is none, median_id = -1 and median_depth = 0.  median_depth is that
+ * record's z, unmapped, bit for bit.
+ * moments [2, H, W] = (A_n, S_n), the backward's state (A_n is the colour
+ * forward's alpha, bit for bit; S_n is relative to z_f).  Every pixel of every
+ * map is written.  n == 0 or num_pairs == 0: GS_OK, the maps are filled with
+ * 0 / -1.  A NULL required pointer, or near / far neither both zero nor
+ * finite with 0 < near < far: GS_ERR_INVALID_ARG before any HIP call. */
+typedef struct gs_distortion_fwd_args {
+  gs_camera cam;                /* the colour forward's (bg is not read) */
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;       /* as gs_blend_fwd_args, after that forward */
+  const uint32_t *sorted_gauss;
+  const float *records;
+  const uint32_t *cell_neval;   /* gs_blend_fwd_args.cell_neval, as written */
+  const uint64_t *live_bits;    /* gs_blend_fwd_args.live_bits, as written, or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;        /* n */
+  float near, far;              /* both 0: linear depth; else the inverse map's planes */
+  float *distortion;            /* [H, W] */
+  float *moments;               /* [2, H, W]: A_n, S_n */
+  float *median_depth;          /* [H, W] */
+  int32_t *median_id;           /* [H, W] */
+} gs_distortion_fwd_args;
+gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream_t stream);
+
+/* Backward over one cell batch, for a cotangent g [H, W] on distortion.  With
+ * A_n, S_n from moments and D = distortion(p):
+ *   X_i = 2 g [m_i (A_{i-1} + A_i - A_n) + S_n - S_i - S_{i-1}]   (= g dD/dc_i)
+ *   K   = 2 g D                                  (Euler: sum_i c_i X_i)
+ *   dL/dalpha_i = T_i (X_i + (P_i - K) / T_{i+1}),  P_i = sum_{j<=i} c_j X_j
+ *                                                (the terminating entry: T_i X_i)
+ *   dL/dm_i = 2 g c_i (A_{i-1} + A_i - A_n)
+ *   dL/dz_i = dL/dm_i * (1 | kappa / z_i^2)      (linear | inverse)
+ * dL/dalpha_i is gs_blend_features_backward's formula with a per-pixel,
+ * per-entry X_i in place of its dot product, chained with the same clamp
+ * masks into (dmu_x, dmu_y, dQ00, dQ01, dQ11, d_opacity).  Nothing flows
+ * through z_f: sum_i dL/dm_i = 0.  Writes one partial per replayed (entry,
+ * cell) in gs_blend_backward's layout, pair_grads[G e + q] = {dmu_x, dmu_y,
+ * dQ00, dQ01, dQ11, d_opacity, 0, 0, 0, d_z}, and sets slot_live[G e + q] = 1
+ * (G = cell_count, q the cell's index in the batch, e the entry's gradient
+ * slot).  No atomics.  gs_gather_partials(accumulate = 1) adds them to the
+ * colour pass's sums (the three +0 leave its colour sums' bits alone), and
+ * the projection backward, its pose form included, chains d_z. */
+typedef struct gs_distortion_bwd_args {
+  gs_camera cam;
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;
+  const uint32_t *sorted_gauss;
+  const float *records;         /* with pair offsets (gs_bin_emit) */
+  const uint32_t *cell_neval;
+  const uint64_t *live_bits;    /* or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;
+  float near, far;              /* the forward's */
+  const float *distortion;      /* [H, W] the forward's output, unmodified */
+  const float *moments;         /* [2, H, W] the forward's */
+  const float *g_distortion;    /* [H, W] dL/ddistortion */
+  float *pair_grads;            /* [T, G, GS_PARTIAL_STRIDE] */
+  uint8_t *slot_live;           /* [T, G], zeroed by the caller */
+  int32_t cell_begin;           /* the batch's first cell */
+  int32_t cell_count;           /* the batch's cells (0 with cell_begin 0: the whole tile) */
+} gs_distortion_bwd_args;
+gs_status gs_blend_distortion_backward(const gs_distortion_bwd_args *a, gs_stream_t stream);
+
 /* ---- Backward of the projection ----------------------------------------
  * Sums each Gaussian's slot partials (slots [pair_offset[g], pair_offset[g]
  * + touches), the groups slot_live flags), adds cotangents on the viewspace_points /

@@ -169,6 +169,27 @@ class GsContribGatherArgs(C.Structure):
     ]
 
 
+class GsDistortionFwdArgs(C.Structure):
+    _fields_ = [
+        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
+        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
+        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("near", C.c_float), ("far", C.c_float), ("distortion", _vp), ("moments", _vp),
+        ("median_depth", _vp), ("median_id", _vp),
+    ]
+
+
+class GsDistortionBwdArgs(C.Structure):
+    _fields_ = [
+        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
+        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
+        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("near", C.c_float), ("far", C.c_float), ("distortion", _vp), ("moments", _vp),
+        ("g_distortion", _vp), ("pair_grads", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32),
+        ("cell_count", C.c_int32),
+    ]
+
+
 GS_POSE_ROW = 16  # doubles per row of gs_project_pose_args.pose_partials; one row per 256 Gaussians
 GS_POSE_BLOCK = 256
 
@@ -313,6 +334,7 @@ EXPORTS = (
     "gs_densify_workspace_bytes", "gs_densify_count", "gs_densify_emit", "gs_density_accumulate",
     "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
     "gs_blend_contributions", "gs_contrib_accumulate",
+    "gs_blend_distortion_forward", "gs_blend_distortion_backward",
     "gs_mcmc_sample", "gs_mcmc_relocate_workspace_bytes", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize",
 )
 
@@ -380,6 +402,8 @@ def _declare(lib):
     lib.gs_gather_feature_partials.argtypes = [P(GsFeatureGatherArgs), _vp]
     lib.gs_blend_contributions.argtypes = [P(GsContribArgs), _vp]
     lib.gs_contrib_accumulate.argtypes = [P(GsContribGatherArgs), _vp]
+    lib.gs_blend_distortion_forward.argtypes = [P(GsDistortionFwdArgs), _vp]
+    lib.gs_blend_distortion_backward.argtypes = [P(GsDistortionBwdArgs), _vp]
     lib.gs_mcmc_sample.argtypes = [P(GsMcmcSampleArgs), _vp]
     lib.gs_mcmc_relocate_workspace_bytes.argtypes = [C.c_int32]
     lib.gs_mcmc_relocate_workspace_bytes.restype = C.c_size_t
@@ -390,7 +414,8 @@ def _declare(lib):
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
               "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
-              "gs_blend_contributions", "gs_contrib_accumulate", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
+              "gs_blend_contributions", "gs_contrib_accumulate", "gs_blend_distortion_forward",
+              "gs_blend_distortion_backward", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
               "gs_mcmc_regularize"):
         getattr(lib, f).restype = C.c_int
 

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 from dataclasses import asdict, dataclass, fields
 from pathlib import Path
+from typing import Optional
 
 try:  # optional, as in the reference (config.py:1-8)
     import yaml
@@ -83,11 +84,20 @@ class TrainingConfig:
     mcmc_opacity_reg: float = 0.01
     mcmc_scale_reg: float = 0.01
     mcmc_grow_factor: float = 1.05
+    # depth distortion (Mip-NeRF 360 / 2DGS): from distortion_from_iter on the loss gains
+    # lambda_distortion * mean over the pixels of sum_ij c_i c_j |m_i - m_j| (render(depth_distortion=True));
+    # m is the camera-space depth, or with distortion_near_far = (near, far) 2DGS's inverse depth.
+    # 0 = off: the step's launches are the ones they were
+    lambda_distortion: float = 0.0
+    distortion_from_iter: int = 0
+    distortion_near_far: Optional[tuple] = None
 
     def __post_init__(self):
         # (a YAML file holds the iterations as a list)
         if isinstance(self.contribution_prune_iterations, list):
             self.contribution_prune_iterations = tuple(self.contribution_prune_iterations)
+        if isinstance(self.distortion_near_far, list):
+            self.distortion_near_far = tuple(self.distortion_near_far)
 
     def check(self) -> None:
         """Values no run can use (the trainer asks at setup)."""
@@ -102,6 +112,17 @@ class TrainingConfig:
         if isinstance(its, (str, bytes)) or not all(isinstance(i, int) and not isinstance(i, bool) and i > 0
                                                     for i in its):
             raise ValueError(f"contribution_prune_iterations must hold positive iteration numbers, got {its!r}")
+        lam = float(self.lambda_distortion)
+        if not (lam >= 0.0 and lam != float("inf")):
+            raise ValueError(f"lambda_distortion must be finite and >= 0, got {self.lambda_distortion!r}")
+        it = self.distortion_from_iter
+        if isinstance(it, bool) or not isinstance(it, int) or it < 0:
+            raise ValueError(f"distortion_from_iter must be an integer >= 0, got {it!r}")
+        nf = self.distortion_near_far
+        if nf is not None:
+            ok = isinstance(nf, (tuple, list)) and len(nf) == 2 and all(isinstance(v, (int, float)) for v in nf)
+            if not (ok and 0.0 < float(nf[0]) < float(nf[1]) < float("inf")):
+                raise ValueError(f"distortion_near_far must be None or finite (near, far) with 0 < near < far, got {nf!r}")
         if self.densify_criterion == "mcmc":
             if isinstance(self.mcmc_cap_max, bool) or not isinstance(self.mcmc_cap_max, int) or self.mcmc_cap_max < 1:
                 raise ValueError(f"mcmc_cap_max must be an integer >= 1, got {self.mcmc_cap_max!r}")

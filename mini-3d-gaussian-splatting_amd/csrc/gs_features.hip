@@ -4,7 +4,9 @@
 //   k_gather_feat  a chunk's partials summed per Gaussian (k_gather_slots' order)
 //   k_contrib      per (entry, cell) the sum, max and count of c over the cell's pixels, and each
 //                  pixel's strongest contributor; k_contrib_gather adds them up per Gaussian
-// Neither blend kernel decides anything of its own: both replay the colour
+//   k_dist_fwd     per pixel the depth distortion sum_ij c_i c_j |m_i - m_j| and the median entry
+//   k_dist_bwd     the distortion's backward, per-pair grad slots in k_blend_bwd's layout
+// No blend kernel here decides anything of its own: all replay the colour
 // forward (k_blend_fwd, gs_blend.hip) over the state it saved -- ranges,
 // sorted_gauss, records, cell_neval, live_bits -- with the operations
 // k_blend_bwd replays it with.  The helpers that form a decision (exp_blend,
@@ -647,6 +649,304 @@ __global__ __launch_bounds__(kBlock) void k_contrib_gather(gs_contrib_gather_arg
   a.views[g] += a.first_batch ? 1 : 0;
 }
 
+// ================================================= depth distortion =======
+// A fourth replay, with a pairwise payload: per pixel
+//   distortion = sum_i sum_j c_i c_j |m_i - m_j| = 2 sum_i c_i (m_i A_{i-1} - S_{i-1}),
+//   A_i = sum_{j<=i} c_j,  S_i = sum_{j<=i} c_j m_j
+// (the lists are sorted by the bits of z and both depth maps are monotone, so
+// the prefix form is the double sum), and the median entry: the first with
+// c > 0 after whose addition the running A >= 0.5, else the last with c > 0.
+// The sum does not change under a shift common to all m, and in fp32 it needs
+// one: the kernels work on differences to the pixel's first contributor f,
+//   m_i = (z_i - z_f) q_i r_f,   linear: q = r = 1;  inverse: q = kappa / z, r = 1 / z
+// (kappa (z_i - z_f) / (z_i z_f) is 2DGS's NDC depth far (z - near) / ((far - near) z)
+// minus its value at z_f), formed from the record depths directly: z_i - z_f
+// is exact or one rounding of a value no larger than the pixel's own depth
+// spread, so every term of A, S and the sum is bounded by that spread, not by
+// the depth.  f is a decision of the replay (the first c > 0), so the forward
+// and the backward take the same one.
+__device__ __forceinline__ float4 dist_payload(float z, uint32_t gid, float kappa) {
+  const bool inv = kappa != 0.f;
+  return make_float4(z, inv ? kappa / z : 1.f, inv ? 1.f / z : 1.f, __uint_as_float(gid));
+}
+
+// k_feat_fwd's walk with (z, q, r, id) as the payload.  kInv: the inverse
+// map (the linear one skips the q r factor).  "A contributor so far" is
+// A > 0 and "the median is taken" is A >= 0.5, both on the A before the entry:
+// no state of their own.
+template <bool kInv>
+__global__ __launch_bounds__(kWave) void k_dist_fwd(gs_distortion_fwd_args a, float kappa) {
+  __shared__ float4 s_rec[kWave * 3];  // per entry: (mx my h00 h11) (ho o - -) (z q r id), h = -q/2
+  Replay r;
+  const CellGeom cg(a.cam.tile_size);
+  const bool any = replay_setup(r, a.cam, a.tiles_x, a.tiles_y, cg.cells(), 0, a.ranges, (uint32_t)a.num_pairs,
+                                a.cell_neval, a.live_bits, a.live_words);
+  if (r.tile >= a.tiles_x * a.tiles_y) return;
+  const int lane = threadIdx.x;
+  const uint32_t ngauss = (uint32_t)a.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  float A = 0.f, S = 0.f, D = 0.f, med_z = 0.f;
+  int med_id = -1;
+  if (any) {
+    const float fx = (float)r.px, fy = (float)r.py;
+    float T1 = 1.f, zf = 0.f, rf = 1.f;
+    bool run = r.inside;  // A < 0.995 so far; lanes outside the tile or image never run
+    float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, nf = n0;
+    auto fetch = [&](uint32_t wd, unsigned long long m) {
+      if ((m >> lane) & 1ull) {
+        const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+        n0 = recs[3 * (size_t)gid];
+        n1 = recs[3 * (size_t)gid + 1];
+        nf = dist_payload(recs[3 * (size_t)gid + 2].y, gid, kappa);
+      }
+    };
+    unsigned long long mcur = r.live_word(0);
+    fetch(0, mcur);
+    for (uint32_t wd = 0; wd < r.nwords; ++wd) {
+      // (this wave's reads of the previous word precede these writes in its in-order LDS queue)
+      if ((mcur >> lane) & 1ull) {
+        s_rec[3 * lane] = make_float4(n0.x, n0.y, -0.5f * n0.z, -0.5f * n0.w);
+        s_rec[3 * lane + 1] = make_float4(-0.5f * n1.x, n1.y, 0.f, 0.f);
+        s_rec[3 * lane + 2] = nf;
+      }
+      const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
+      fetch(wd + 1u, mnext);  // in flight while this word composites
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
+      unsigned long long m = mcur;
+      while (m) {
+        const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+        m &= m - 1ull;
+        const float4 c0 = s_rec[3 * bit], c1 = s_rec[3 * bit + 1], fv = s_rec[3 * bit + 2];
+        const float dx = fx - c0.x, dy = fy - c0.y;
+        const float t = conic_s(dx, dy, c0.z, c1.x, c0.w);  // -s/2 (:333)
+        const bool lv = run && !(t < kSkipT);                // the :336 skip, decided on s
+        const float w = sat01(exp_blend(t));                 // :334
+        const float ai = lv ? sat01(c1.y * w) : 0.f;         // :339
+        const float c = T1 * ai;                             // :343-344 (T1 = 1 - A)
+        // until the first contributor (A == 0) the reference follows the entry: m = 0, and c = +0
+        const bool have = A > 0.f;
+        zf = have ? zf : fv.x;
+        float md = fv.x - zf;
+        if constexpr (kInv) {
+          rf = have ? rf : fv.z;
+          md *= fv.y * rf;
+        }
+        D = __builtin_fmaf(c, __builtin_fmaf(md, A, -S), D);
+        S = __builtin_fmaf(c, md, S);
+        if (c > 0.f && A < 0.5f) {  // (A before this entry: the median is not taken yet)
+          med_id = (int)__float_as_uint(fv.w);
+          med_z = fv.x;
+        }
+        A = A + c;
+        T1 = 1.f - A;
+        run = run && A < kAlphaStop;                         // the :352 break
+      }
+      asm volatile("" ::: "memory");
+      mcur = mnext;
+    }
+  }
+  if (!r.inside) return;
+  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
+  const size_t p = (size_t)r.py * a.cam.image_width + r.px;
+  a.distortion[p] = 2.f * D;
+  a.moments[p] = A;
+  a.moments[HW + p] = S;
+  a.median_depth[p] = med_z;
+  a.median_id[p] = med_id;
+}
+
+__global__ __launch_bounds__(kBlock) void k_dist_empty(gs_distortion_fwd_args a, long long pixels) {
+  const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (p < pixels) {
+    a.distortion[p] = 0.f;
+    a.moments[p] = 0.f;
+    a.moments[pixels + p] = 0.f;
+    a.median_depth[p] = 0.f;
+    a.median_id[p] = -1;
+  }
+}
+
+// k_feat_bwd's two phases with a per-pixel, per-entry X_i in place of the
+// payload's dot product, for a cotangent g on the distortion:
+//   X_i = 2 g [m_i (A_{i-1} + A_i - A_n) + S_n - S_i - S_{i-1}]   (= g dD/dc_i),  K = 2 g D
+//   dL/dm_i = 2 g c_i (A_{i-1} + A_i - A_n),  dL/dz_i = dL/dm_i q_i r_i   (1 | kappa / z_i^2)
+// dL/dm_i depends on the pixel, so phase A hands phase B a third value per
+// (entry, pixel) beside (dop, +-c).  Nothing flows through the reference
+// depth: sum_i dL/dm_i = 0.
+template <bool kInv>
+__global__ __launch_bounds__(kWave) void k_dist_bwd(gs_distortion_bwd_args a, float kappa) {
+  __shared__ float2 s_dc[kBwdGroup][kBwdRow];  // per group entry and pixel: (dop, c)
+  __shared__ float s_dm[kBwdGroup][kBwdRow];   // ... and dL/dm
+  __shared__ float2 s_wrec[kBwdGroup * 6];     // the group's records: (mx my h00 h11) (ho o z q) (r - slot -)
+  Replay r;
+  const int ncell = a.cell_count;
+  if (!replay_setup(r, a.cam, a.tiles_x, a.tiles_y, ncell, a.cell_begin, a.ranges, (uint32_t)a.num_pairs,
+                    a.cell_neval, a.live_bits, a.live_words))
+    return;
+  const int qb = r.quad - a.cell_begin;  // the cell's partial group
+  const int lane = threadIdx.x;
+  const uint32_t ngauss = (uint32_t)a.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  // the pixel's cotangent and the forward's state (lanes outside read pixel 0, unused)
+  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
+  const size_t p = r.inside ? (size_t)r.py * a.cam.image_width + r.px : 0;
+  const float g2 = r.inside ? 2.f * a.g_distortion[p] : 0.f;
+  const float An = a.moments[p], Sn = a.moments[HW + p];
+  const float fx = (float)r.px, fy = (float)r.py;
+  // PG = P - K as one running sum (k_feat_bwd), K = 2 g D
+  float PG = -(g2 * a.distortion[p]);
+  float A = 0.f, S = 0.f, T1 = 1.f, zf = 0.f, rf = 1.f;
+  bool run = r.inside;
+  float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, rz = r0;
+  auto fetch = [&](uint32_t wd, unsigned long long m) {
+    if ((m >> lane) & 1ull) {
+      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+      r0 = recs[3 * (size_t)gid];
+      r1 = recs[3 * (size_t)gid + 1];
+      r2 = recs[3 * (size_t)gid + 2];
+      rz = dist_payload(r2.y, gid, kappa);
+    }
+  };
+  // Phase B over a group: its k live entries, staged at s_wrec positions 0 .. k - 1.
+  auto phase_b = [&](int k) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
+    const int j = lane / kBwdLanes, col = lane % kBwdLanes;
+    if (j < k) {
+      const uint32_t e = (uint32_t)j;
+      const float4 ia = reinterpret_cast<const float4 *>(s_wrec)[3 * e];  // mx my h00 h11 (h = -q/2)
+      const float4 ib = reinterpret_cast<const float4 *>(s_wrec)[3 * e + 1];  // ho o z q
+      const float q00 = -2.f * ia.z, q11 = -2.f * ia.w, qo = -2.f * ib.x;  // (exact)
+      const float zr = s_wrec[6 * e + 4].x;
+      const uint32_t slot = __float_as_uint(s_wrec[6 * e + 5].x);
+      const float hop = -0.5f * ib.y;
+      // (k_feat_bwd's column walk: the row moments about the column row nearest the mean)
+      const float bx = (float)(r.x0 + col) - ia.x;
+      const float rc = __builtin_amdgcn_fmed3f(__builtin_rintf(ia.y - (float)r.y0), 0.f, (float)(kBwdGroup - 1));
+      float S0 = 0.f, Soy = 0.f, Soyy = 0.f, g5 = 0.f, g9 = 0.f;
+#pragma unroll
+      for (int row = 0; row < kBwdGroup; ++row) {
+        const int pp = col + 8 * row;  // phase A's lane of that pixel
+        const float2 dc = s_dc[j][pp];
+        const float dop = dc.x, cs = dc.y;
+        const float ds = cs > 0.f ? dop : 0.f;
+        const float wr = (float)row - rc;  // exact: small integers
+        S0 += ds;
+        Soy = __builtin_fmaf(ds, wr, Soy);
+        Soyy = __builtin_fmaf(ds, wr * wr, Soyy);
+        g5 += dop;
+        g9 += s_dm[j][pp];
+      }
+      S0 *= hop;
+      Soy *= hop;
+      Soyy *= hop;
+      const float by = (float)r.y0 + rc - ia.y;
+      float Sx = bx * S0, Sy = __builtin_fmaf(by, S0, Soy);
+      float g2s = bx * Sx, g3 = bx * Sy;
+      float g4 = __builtin_fmaf(by, __builtin_fmaf(by, S0, 2.f * Soy), Soyy);
+      Sx = oct_sum(Sx); Sy = oct_sum(Sy); g2s = oct_sum(g2s); g3 = oct_sum(g3); g4 = oct_sum(g4);
+      g5 = oct_sum(g5); g9 = oct_sum(g9);
+      if (col == 0) {
+        const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
+        const size_t sq = (size_t)slot * (uint32_t)ncell + (uint32_t)qb;
+        if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+          float *out = a.pair_grads + sq * GS_PARTIAL_STRIDE;  // (dense 40-B partials, 8-B aligned: f4_u8)
+          *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2s, g3};
+          *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, 0.f, 0.f};
+          *reinterpret_cast<f2_u8 *>(out + 8) = f2_u8{0.f, kInv ? g9 * (ib.w * zr) : g9};  // dm/dz = q r
+          a.slot_live[sq] = 1;
+        }
+      }
+    }
+  };
+  unsigned long long mcur = r.live_word(0);
+  fetch(0, mcur);
+  for (uint32_t wd = 0; wd < r.nwords; ++wd) {
+    // the entry's gradient slot, as k_feat_bwd forms it
+    const bool mine = (mcur >> lane) & 1ull;
+    const uint32_t info = __float_as_uint(r2.w);
+    const uint32_t slot = __float_as_uint(r2.z) + (r.ty - ((info >> 12) & 0xFFFu)) * ((info >> 24) + 1u) +
+                          (r.tx - (info & 0xFFFu));
+    const uint32_t rank =
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
+    const float4 c0 = make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
+    const float4 c1 = make_float4(-0.5f * r1.x, r1.y, rz.x, rz.y);
+    const float4 c2 = make_float4(rz.z, 0.f, __uint_as_float(slot), 0.f);
+    const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
+    fetch(wd + 1u, mnext);  // in flight while this word replays
+    unsigned long long m = mcur;
+    uint32_t kb = 0;  // packed position of the group's first entry
+    while (m) {
+      int k = 0;
+      // (the previous group's reads came before these writes in this wave's in-order LDS queue)
+      if (mine && rank - kb < (uint32_t)kBwdGroup) {
+        float4 *d = reinterpret_cast<float4 *>(&s_wrec[6 * (rank - kb)]);
+        d[0] = c0;
+        d[1] = c1;
+        d[2] = c2;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
+      const char *cb = reinterpret_cast<const char *>(s_wrec);
+#pragma unroll
+      for (int kk = 0; kk < kBwdGroup; ++kk) {
+        if (kk > 0 && !m) break;
+        m &= m - 1ull;
+        const float4 r0v = reinterpret_cast<const float4 *>(cb + 48 * kk)[0];
+        const float4 r1v = reinterpret_cast<const float4 *>(cb + 48 * kk)[1];
+        const float zr = reinterpret_cast<const float2 *>(cb + 48 * kk)[4].x;
+        const float dx = fx - r0v.x, dy = fy - r0v.y;
+        const float tq = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
+        const bool live = run && !(tq < kSkipT);
+        const float e = exp_blend(tq);
+        const float w = sat01(e);
+        const float u = r1v.y * w;
+        const float ai = sat01(u);
+        const float trans = T1;
+        const float c = trans * (live ? ai : 0.f);
+        // the forward's reference and prefix sums, operation for operation
+        const bool have = A > 0.f;
+        zf = have ? zf : r1v.z;
+        float md = r1v.z - zf;
+        if constexpr (kInv) {
+          rf = have ? rf : zr;
+          md *= r1v.w * rf;
+        }
+        const float Ap = A, Sp = S;
+        S = __builtin_fmaf(c, md, S);
+        A = A + c;
+        const float u3 = (Ap + A) - An;
+        const float X = g2 * __builtin_fmaf(md, u3, (Sn - S) - Sp);
+        PG = __builtin_fmaf(c, X, PG);
+        const bool term = !(A < kAlphaStop);
+        T1 = 1.f - A;
+        const float inv = __builtin_amdgcn_rcpf(T1);  // v_rcp_f32 (1 ulp): a gradient factor, no decision
+        const float d_live = __builtin_fmaf(inv, PG, X);
+        // the terminating contributor has nothing behind it
+        const float dal = trans * (term ? X : d_live);
+        run = run && !term;
+        const float g = (ai == u) ? dal * w : 0.f;
+        const float dop = (c > 0.f) ? g : 0.f;
+        const float cw = (w == e) ? c : -c;  // c == +0 when skipped
+        s_dc[kk][lane] = make_float2(dop, cw);
+        s_dm[kk][lane] = (g2 * c) * u3;
+        k = kk + 1;
+      }
+      phase_b(k);
+      kb += (uint32_t)k;
+    }
+    mcur = mnext;
+  }
+}
+
+// near == far == 0: the linear map (kappa 0); else 0 < near < far, both finite
+bool near_far_ok(float near, float far) {
+  if (near == 0.f && far == 0.f) return true;
+  return near > 0.f && far > near && far <= 3.402823466e+38f;  // (false for NaN)
+}
+
+float near_far_kappa(float near, float far) {
+  return (near == 0.f && far == 0.f) ? 0.f : (float)((double)far * near / ((double)far - near));
+}
+
 int cells_per_tile(int tile_size) {
   const int qx = (tile_size + GS_QUAD - 1) / GS_QUAD;
   return qx * qx;
@@ -763,6 +1063,64 @@ gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream) {
     return gs_internal_check_launch(me);
   }
   k_contrib<<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b);
+  return gs_internal_check_launch(me);
+}
+
+gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream_t stream) {
+  const char *me = "gs_blend_distortion_forward";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
+  if (!near_far_ok(a->near, a->far))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: near / far must both be 0 (linear depth) or finite with 0 < near < far", me);
+  if (!a->ranges || !a->records || !a->cell_neval || !a->distortion || !a->moments || !a->median_depth ||
+      !a->median_id || (a->live_bits && a->live_words <= 0) || (a->num_pairs > 0 && !a->sorted_gauss))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (a->num_pairs < 0 || a->num_gaussians < 0)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or num_gaussians", me);
+  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
+  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
+  const long long blocks = (long long)div_up((long long)a->tiles_x * a->tiles_y, 8) * 8LL * cells_per_tile(a->cam.tile_size);
+  // (a launch's work-items, workgroups x 64, must stay below 2^32)
+  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  if (a->num_gaussians == 0 || a->num_pairs == 0) {
+    const long long pixels = (long long)a->cam.image_width * a->cam.image_height;
+    k_dist_empty<<<div_up(pixels, kBlock), kBlock, 0, (hipStream_t)stream>>>(*a, pixels);
+    return gs_internal_check_launch(me);
+  }
+  const float kappa = near_far_kappa(a->near, a->far);
+  if (kappa != 0.f)
+    k_dist_fwd<true><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(*a, kappa);
+  else
+    k_dist_fwd<false><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(*a, 0.f);
+  return gs_internal_check_launch(me);
+}
+
+gs_status gs_blend_distortion_backward(const gs_distortion_bwd_args *a, gs_stream_t stream) {
+  const char *me = "gs_blend_distortion_backward";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
+  if (!near_far_ok(a->near, a->far))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: near / far must both be 0 (linear depth) or finite with 0 < near < far", me);
+  if (!a->ranges || !a->sorted_gauss || !a->records || !a->cell_neval || !a->distortion || !a->moments ||
+      !a->g_distortion || !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (a->num_pairs < 0 || a->num_gaussians < 1)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
+  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
+  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
+  const int cells = cells_per_tile(a->cam.tile_size);
+  gs_distortion_bwd_args b = *a;
+  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
+  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
+                "[0, gs_tile_quads(tile_size))", me);
+  const long long blocks = (long long)div_up((long long)b.tiles_x * b.tiles_y, 8) * 8LL * b.cell_count;
+  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  const float kappa = near_far_kappa(b.near, b.far);
+  if (kappa != 0.f)
+    k_dist_bwd<true><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b, kappa);
+  else
+    k_dist_bwd<false><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b, 0.f);
   return gs_internal_check_launch(me);
 }
 

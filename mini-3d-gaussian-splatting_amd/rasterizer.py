@@ -466,10 +466,122 @@ def _contribution_pass(cam: CameraParams, fr: "_Frame", n: int, cp: _Contributio
     StageTimer.mark("~end_contrib")
 
 
+def check_distortion_near_far(near_far) -> Tuple[float, float]:
+    """(near, far) of the distortion's depth map as the kernels take them:
+    (0, 0), linear depth, for None; else two finite numbers with
+    0 < near < far (the inverse map) -- anything else is a ValueError."""
+    if near_far is None:
+        return 0.0, 0.0
+    try:
+        near, far = (float(v) for v in near_far)
+    except (TypeError, ValueError):
+        raise ValueError(f"distortion_near_far must be None or (near, far), got {near_far!r}") from None
+    if not (math.isfinite(near) and math.isfinite(far) and 0.0 < near < far):
+        raise ValueError(f"distortion_near_far needs finite 0 < near < far, got {near_far!r}")
+    return near, far
+
+
+class _DistortionPass:
+    """What one render asked of the distortion pass (the depth map's planes)
+    and, after the forward, its non-differentiable maps: median_depth,
+    median_id, and moments [2, H, W] = (A_n, S_n), the backward's state."""
+    __slots__ = ("near", "far", "moments", "median_depth", "median_id")
+
+    def __init__(self, near_far=None):
+        self.near, self.far = check_distortion_near_far(near_far)
+        self.moments = self.median_depth = self.median_id = None
+
+
+class _DistortionGrad:
+    """One backward's view of a frame's distortion pass: the pass, the
+    forward's distortion map and its cotangent."""
+    __slots__ = ("dp", "out", "g_out")
+
+    def __init__(self, dp, out, g_out):
+        self.dp, self.out, self.g_out = dp, out, g_out
+
+
+def _live_words(fr) -> int:
+    return 0 if fr.live_bits is None else fr.live_bits.shape[1]
+
+
+def _distortion_forward(cam: CameraParams, fr: "_Frame", n: int, dp: _DistortionPass, dev) -> torch.Tensor:
+    """The distortion map [H, W] of a stage-path frame, and dp's maps: one
+    gs_blend_distortion_forward over the state the colour forward left in
+    `fr` (zeros / -1 when nothing was drawn)."""
+    H, W, f32 = int(cam.image_height), int(cam.image_width), torch.float32
+    fr.distortion = dp  # (where the tests read the moments)
+    if fr.M == 0 or fr.T == 0:
+        dp.moments = torch.zeros((2, H, W), dtype=f32, device=dev)
+        dp.median_depth = torch.zeros((H, W), dtype=f32, device=dev)
+        dp.median_id = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+        return torch.zeros((H, W), dtype=f32, device=dev)
+    out = torch.empty((H, W), dtype=f32, device=dev)
+    dp.moments = torch.empty((2, H, W), dtype=f32, device=dev)
+    dp.median_depth = torch.empty((H, W), dtype=f32, device=dev)
+    dp.median_id = torch.empty((H, W), dtype=torch.int32, device=dev)
+    fa = N.GsDistortionFwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                               N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits), _live_words(fr), fr.T, n,
+                               dp.near, dp.far, N.ptr(out), N.ptr(dp.moments), N.ptr(dp.median_depth),
+                               N.ptr(dp.median_id))
+    StageTimer.mark("distortion_fwd")
+    N.check(N.load().gs_blend_distortion_forward(C.byref(fa), _stream()), "gs_blend_distortion_forward")
+    StageTimer.mark("~end_distortion_fwd")
+    return out
+
+
+def _distortion_backward(lib, cam: CameraParams, fr: "_Frame", dist: _DistortionGrad, n: int, pair_grads, slot_live,
+                         sums, s) -> torch.Tensor:
+    """The distortion's backward over a stage-path frame: per cell batch (the
+    frame's own plan: fr.groups cells at a time) one
+    gs_blend_distortion_backward and one gs_gather_partials that adds its
+    partials to the sums so far.  Returns grad_sums [n, 10] for the projection
+    backward.  pair_grads / slot_live: the colour pass's one-batch partials,
+    not yet gathered (gathered here first, then the buffer is reused), or
+    None; sums: the sums gathered so far (the colour pass's batches, the
+    feature pass's), or None.  The flags are this call's own scratch, cleared
+    before every launch."""
+    dev = dist.out.device
+    f32 = torch.float32
+    G, Q, T = fr.groups, cam.cells, fr.T
+    have = sums is not None
+    grad_sums = sums if have else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
+    ga = N.GsProjectBwdArgs()
+    ga.g.n = n
+    ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
+    ga.grad_sums = N.ptr(grad_sums)
+    if pair_grads is not None:
+        ga.pair_grads, ga.slot_live, ga.partial_groups = N.ptr(pair_grads), N.ptr(slot_live), G
+        N.check(lib.gs_gather_partials(C.byref(ga), 1 if have else 0, s), "gs_gather_partials")
+        have = True
+    if pair_grads is None or pair_grads.shape[0] < T * G:
+        pair_grads = torch.empty((T * G, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
+    flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
+    g_out = dist.g_out
+    if g_out.dtype != f32 or not g_out.is_contiguous():
+        g_out = g_out.to(f32).contiguous()
+    dp = dist.dp
+    ba = N.GsDistortionBwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                               N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits), _live_words(fr), T, n,
+                               dp.near, dp.far, N.ptr(dist.out), N.ptr(dp.moments), N.ptr(g_out), N.ptr(pair_grads),
+                               N.ptr(flags), 0, 0)
+    ga.pair_grads, ga.slot_live = N.ptr(pair_grads), N.ptr(flags)
+    StageTimer.mark("distortion_bwd")
+    for c0 in range(0, Q, G):
+        ba.cell_begin, ba.cell_count = c0, min(G, Q - c0)
+        ga.partial_groups = ba.cell_count
+        flags.zero_()
+        N.check(lib.gs_blend_distortion_backward(C.byref(ba), s), "gs_blend_distortion_backward")
+        N.check(lib.gs_gather_partials(C.byref(ga), 1 if have else 0, s), "gs_gather_partials")
+        have = True
+    StageTimer.mark("~end_distortion_bwd")
+    return grad_sums
+
+
 class _Frame:
     """Intermediate device buffers of one forward, kept for the backward."""
     __slots__ = ("records", "rects", "vis", "pair_offset", "order", "ranges", "sorted_gauss", "pix_flags",
-                 "cell_neval", "live_bits", "big", "M", "T", "slot_live", "groups", "consumed")
+                 "cell_neval", "live_bits", "big", "M", "T", "slot_live", "groups", "consumed", "distortion")
 
 
 _T_SEEN: dict = {}  # device -> tile entries T of its last frame (capacity guess)
@@ -1028,8 +1140,12 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
 
 def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotation, logits, opacity,
                       means2d, conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit=False,
-                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None, feat=None, density=None):
-    """density: optional (DensityStats, the forward's radii): the view is added
+                      sh_rest=None, sh_degree=0, out=None, outputs=None, d_view=None, feat=None, density=None,
+                      dist=None):
+    """dist: optional _DistortionGrad with a cotangent on the distortion map (a
+    stage-path frame): its geometry, opacity and depth sums are added to the
+    colour pass's (and the feature pass's) before the one projection backward.
+    density: optional (DensityStats, the forward's radii): the view is added
     to the statistics after the projection backward's last row range.
     outputs: the forward's (image, alpha, depth), unmodified -- with the
     frame's clamp flags they are the blend backward's per-pixel state.
@@ -1112,6 +1228,11 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
         grad_sums, pair_grads, slot_live = batch_sums, None, None  # (summed batch by batch above)
     else:
         grad_sums = None if pair_grads is None else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
+    if dist is not None and fr.M > 0 and fr.T > 0:
+        # (partials not yet gathered go first, into the buffer made for them; sums gathered above are added to)
+        grad_sums = _distortion_backward(lib, cam, fr, dist, n, pair_grads, slot_live,
+                                         grad_sums if pair_grads is None else None, s)
+        pair_grads = slot_live = None
     pb = N.GsProjectBwdArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(fr.vis), N.ptr(fr.rects),
                             # Gaussian order (order=NULL): inputs/outputs stream; walking in depth
                             # order coalesces the slot reads but scatters 10 arrays (measured 2.4x slower)
@@ -1401,7 +1522,9 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None,
+                distort=None):
+        # distort: a _DistortionPass: a ninth output, the distortion map, follows the feature image
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=True)
@@ -1409,22 +1532,26 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
         n, channels = int(features.shape[0]), int(features.shape[1])
         staged = _stage_features(features)
         feat_image = _feature_forward(cam, fr, staged, channels, n, xyz.device)
+        dist_out = () if distort is None else (_distortion_forward(cam, fr, n, distort, xyz.device),)
         if contrib is not None:
             _contribution_pass(cam, fr, n, contrib, xyz.device)
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
         ctx.feature_shape = (n, channels)
+        ctx.distort = distort
         ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[12] else None
         ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
-                              depth, staged, feat_image)
+                              depth, staged, feat_image, *dist_out)
         ctx.mark_non_differentiable(radii, vis)
         ctx.set_materialize_grads(False)
-        return image, alpha, depth, means2d, conics, radii, vis, feat_image
+        return (image, alpha, depth, means2d, conics, radii, vis, feat_image) + dist_out
 
     @staticmethod
-    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, g_features):
+    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, g_features, *g_dist):
         (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth, staged,
-         feat_image) = ctx.saved_tensors
+         feat_image, *dist_out) = ctx.saved_tensors
+        # (no cotangent on the distortion map: no launch for it)
+        dist = _DistortionGrad(ctx.distort, dist_out[0], g_dist[0]) if g_dist and g_dist[0] is not None else None
         g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
         dest = ctx.grad_dest() if ctx.grad_dest is not None else None
         d_view = None
@@ -1436,7 +1563,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
             sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, feat=feat,
-            density=ctx.density)
+            density=ctx.density, dist=dist)
         need = ctx.needs_input_grad
         d_features = None
         if need[7] and feat is not None:
@@ -1455,7 +1582,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                d_features, None, None, None, None, g_view, None, None)
+                d_features, None, None, None, None, g_view, None, None, None)
 
 
 class RasterizeGaussians(torch.autograd.Function):
@@ -1464,9 +1591,11 @@ class RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None):
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None,
+                distort=None):
         # contrib: a _ContributionPass: the frame is then the stage path's (the same bits) and the
         # contribution pass runs at the end of this forward
+        # distort: a _DistortionPass: the stage path too, and an eighth output, the distortion map
         # density_stats: a DensityStats this frame's backward adds the view to (it needs the
         # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape)
         # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
@@ -1474,24 +1603,30 @@ class RasterizeGaussians(torch.autograd.Function):
         # reads the pose from `cam`, whose values are the same
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
-            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=contrib is not None)
+            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]),
+            stage_path=contrib is not None or distort is not None)
+        dist_out = () if distort is None else (_distortion_forward(cam, fr, int(xyz.shape[0]), distort, xyz.device),)
         if contrib is not None:
             _contribution_pass(cam, fr, int(xyz.shape[0]), contrib, xyz.device)
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
+        ctx.distort = distort
         ctx.density = None if density_stats is None else (density_stats, radii)
         ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[11] else None
         # (the outputs image / alpha / depth too: the blend backward's per-pixel
         # state; autograd refuses the backward if they were modified in place)
         ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
-                              depth)
+                              depth, *dist_out)
         ctx.mark_non_differentiable(radii, vis)
         ctx.set_materialize_grads(False)
-        return image, alpha, depth, means2d, conics, radii, vis
+        return (image, alpha, depth, means2d, conics, radii, vis) + dist_out
 
     @staticmethod
-    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis):
-        xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth = ctx.saved_tensors
+    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, *g_dist):
+        (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth,
+         *dist_out) = ctx.saved_tensors
+        # (no cotangent on the distortion map: no launch for it)
+        dist = _DistortionGrad(ctx.distort, dist_out[0], g_dist[0]) if g_dist and g_dist[0] is not None else None
         g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
         dest = ctx.grad_dest() if ctx.grad_dest is not None else None
         d_view = None
@@ -1500,7 +1635,8 @@ class RasterizeGaussians(torch.autograd.Function):
         d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, None if g_alpha is None else g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
-            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, density=ctx.density)
+            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, density=ctx.density,
+            dist=dist)
         need = ctx.needs_input_grad
         g_view = None
         if d_view is not None:
@@ -1514,13 +1650,26 @@ class RasterizeGaussians(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                None, None, None, None, g_view, None, None)
+                None, None, None, None, g_view, None, None, None)
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
               sh_rest=None, sh_degree=0, grad_dest=None, view=None, features=None, density_stats=None,
-              contribution_stats=None, dominant=False):
-    """contribution_stats: optional ContributionStats of N Gaussians on their
+              contribution_stats=None, dominant=False, depth_distortion=False, distortion_near_far=None):
+    """depth_distortion=True: three more outputs follow (after the feature
+    image, when there is one, and before the dominant maps): the fp32 [H, W]
+    depth distortion sum_i sum_j c_i c_j |m_i - m_j| of each pixel's
+    contributors (gs_blend_distortion_forward; differentiable in the geometry,
+    the opacity and, through d_z and the weights, `view`), the fp32 [H, W]
+    median depth and the int32 [H, W] median Gaussian (-1: none), neither with
+    a gradient.  m is the camera-space depth, or with
+    distortion_near_far=(near, far) 2DGS's inverse (NDC) depth; a bad pair, or
+    one without depth_distortion, is a ValueError before any launch.  The frame
+    takes the stage path (the seven standard outputs and their gradients are
+    the same bits); the distortion's backward runs only when the map received
+    a cotangent, and density_stats then see the summed dL/dmeans2d, the
+    distortion's part included.
+    contribution_stats: optional ContributionStats of N Gaussians on their
     device (checked here, before any launch): the forward ends with the
     contribution pass, which adds this view's per-Gaussian blend weights to
     it (sum, max, pixel count, views).  dominant=True: two more outputs follow
@@ -1572,6 +1721,9 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
         _check_density_stats(density_stats, n, xyz.device)
     if contribution_stats is not None:
         _check_contribution_stats(contribution_stats, n, xyz.device)
+    if distortion_near_far is not None and not depth_distortion:
+        raise ValueError("distortion_near_far needs depth_distortion=True")
+    dp = _DistortionPass(distortion_near_far) if depth_distortion else None
     xyz = prep("xyz", xyz, (3,))
     cov3d = prep("cov3d", cov3d, (3, 3))
     scaling = prep("scaling", scaling, (3,))
@@ -1615,6 +1767,8 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     cp = _ContributionPass(contribution_stats, dominant) if (contribution_stats is not None or dominant) else None
     if cp is not None:
         stats = (density_stats, cp)
+    if dp is not None:
+        stats = (density_stats, cp, dp)
     if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
         if stats:
             stats = (None,) + stats
@@ -1631,6 +1785,8 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     else:
         outs = RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
                                         bool(opacity_is_logit), sh_degree, grad_dest, *stats)
+    if dp is not None:
+        outs = tuple(outs) + (dp.median_depth, dp.median_id)
     if cp is not None and cp.dominant:
         outs = tuple(outs) + (cp.dominant_id, cp.dominant_weight)
     return outs

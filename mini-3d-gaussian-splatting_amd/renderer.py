@@ -28,6 +28,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     "features": F [N, C] composited with the colour pass's own weights.
   * `render(..., density_stats=S)` (not in the reference) adds the view to the
     density-control statistics S at the end of its backward (DensityStats).
+  * `render(..., depth_distortion=True)` (not in the reference) also returns
+    "distortion", "median_depth" and "median_gaussian".
   * `settings.screen_filter` (not in the reference; default 0 = off) low-pass
     filters every splat in screen space, cov2d + s I, and with
     `settings.filter_compensate` keeps its energy (anti-aliasing).
@@ -45,7 +47,8 @@ from typing import Dict, Optional
 import torch
 
 from . import _native as N
-from .rasterizer import CameraParams, ContributionStats, DensityStats, check_screen_filter, rasterize
+from .rasterizer import (CameraParams, ContributionStats, DensityStats, check_distortion_near_far,
+                         check_screen_filter, rasterize)
 
 
 @dataclass
@@ -152,8 +155,32 @@ class GaussianRenderer:
                features: Optional[torch.Tensor] = None,
                density_stats: Optional[DensityStats] = None,
                contribution_stats: Optional[ContributionStats] = None,
-               dominant: bool = False) -> Dict[str, torch.Tensor]:
-        """contribution_stats: optional ContributionStats of the model's size
+               dominant: bool = False, depth_distortion: bool = False,
+               distortion_near_far=None) -> Dict[str, torch.Tensor]:
+        """depth_distortion: the result also holds
+          "distortion"      fp32 [H, W]: sum_i sum_j c_i c_j |m_i - m_j| over
+                            the pixel's contributors, with the colour pass's
+                            own weights c -- how spread out along the ray they
+                            are (the Mip-NeRF 360 / 2DGS distortion loss is its
+                            mean).  Differentiable in the geometry, the opacity
+                            and, through the depths and the weights, the pose.
+          "median_depth"    fp32 [H, W]: the camera-space depth of the
+                            Gaussian at which the accumulated opacity reaches
+                            one half (the last contributor where it never
+                            does, 0 where there is none).  No gradient.
+          "median_gaussian" int32 [H, W]: that Gaussian's index, -1 for none.
+        m is the camera-space depth z, or with distortion_near_far=(near, far),
+        finite with 0 < near < far, 2DGS's inverse depth
+        far (z - near) / ((far - near) z).  A differentiable median depth is one
+        gather of the camera-space z in torch:
+          z_cam = (xyz @ R.T + t)[:, 2];  z_cam[out["median_gaussian"].clamp_min(0).long()]
+        The frame takes the stage path, as with features=: the seven standard
+        outputs and their gradients are the same bits, and the distortion's
+        backward runs only when "distortion" takes part in the loss.  With
+        density_stats the statistics see the summed dL/d(viewspace_points),
+        the distortion's part included.  A bad distortion_near_far, or one
+        without depth_distortion, is a ValueError before anything is launched.
+        contribution_stats: optional ContributionStats of the model's size
         on its device.  The forward of this render then ends with the
         contribution pass: per Gaussian, the sum and the maximum over the
         image of its blend weight c_i(p) -- the weights the colour pass
@@ -186,6 +213,10 @@ class GaussianRenderer:
         normalisation (a feature background b is the caller's
         out["features"] + (1 - out["alpha"]) * b).  Gradients reach the
         features and, through the weights, the geometry and the pose."""
+        if distortion_near_far is not None:
+            if not depth_distortion:
+                raise ValueError("distortion_near_far needs depth_distortion=True")
+            check_distortion_near_far(distortion_near_far)
         wv = _world_view(camera)
         cam = camera_params(camera, settings, self.radius_min, self.radius_max, self.tile_size, world_view=wv)
         # a view on the autograd tape receives its gradient (the reference's
@@ -250,6 +281,8 @@ class GaussianRenderer:
             extra["contribution_stats"] = contribution_stats
         if dominant:
             extra["dominant"] = True
+        if depth_distortion:
+            extra["depth_distortion"], extra["distortion_near_far"] = True, distortion_near_far
         image, alpha, depth, means2d, conics, radii, vis, *feature_image = rasterize(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
             sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **extra)
@@ -273,6 +306,9 @@ class GaussianRenderer:
         if dominant:
             out["dominant_gaussian"], out["dominant_weight"] = feature_image[-2:]
             feature_image = feature_image[:-2]
+        if depth_distortion:
+            out["distortion"], out["median_depth"], out["median_gaussian"] = feature_image[-3:]
+            feature_image = feature_image[:-3]
         if feature_image:
             out["features"] = feature_image[0]
         return out

@@ -11,7 +11,9 @@ render's backward adds to gaussians.density_stats (then also
 prune_screen_radius and, every opacity_reset_interval iterations, the 3DGS
 opacity reset), or with densify_criterion = "mcmc" the 3DGS-MCMC family
 (_mcmc_update: regularisers, relocation and capped growth in place of split /
-clone / prune, position noise every iteration).  Nothing in a step reads a value
+clone / prune, position noise every iteration).  With lambda_distortion > 0 the
+loss gains, from distortion_from_iter on, lambda_distortion times the mean
+depth distortion of the view (render(depth_distortion=True)).  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.
 
 Data parallel: with torch.distributed initialised,
@@ -124,12 +126,20 @@ class GaussianTrainer:
                 self._reducer = GradAllReduce(params, self._dist).attach(g)
                 self._reducer_n = g.get_num_points()
             self._reducer.params = params
+        extra = {}
         if c.densify_criterion == "screen":
-            out = self.renderer.render(camera, g, self._settings(camera), density_stats=g.density_stats)
-        else:
-            out = self.renderer.render(camera, g, self._settings(camera))
+            extra["density_stats"] = g.density_stats
+        # the distortion term: the eager stage path (no replayed step renders it)
+        distort = c.lambda_distortion > 0 and self.iteration >= c.distortion_from_iter
+        if distort:
+            extra["depth_distortion"] = True
+            if c.distortion_near_far is not None:
+                extra["distortion_near_far"] = c.distortion_near_far
+        out = self.renderer.render(camera, g, self._settings(camera), **extra)
         target = camera._image
         total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
+        if distort:
+            total = total + c.lambda_distortion * out["distortion"].mean()
         total.backward()
         opt.update_learning_rate(self.iteration)
         if c.densify_criterion == "mcmc":
