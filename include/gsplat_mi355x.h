@@ -310,7 +310,10 @@ typedef struct gs_blend_fwd_args {
                                    blocks the gradient), bit 3 likewise for alpha */
   uint32_t *cell_neval;         /* [num_tiles * gs_tile_quads(tile_size)]: per (tile, 8x8 cell q),
                                    at tile * cells + q, the entries of the tile's list up to the last
-                                   one any of the cell's pixels evaluated */
+                                   one any of the cell's pixels evaluated: the largest pix_neval
+                                   among the cell's pixels inside the tile and the image (the
+                                   list's length if one of them never reached A >= 0.995; 0 for a
+                                   cell wholly outside) */
   uint64_t *live_bits;          /* [gs_tile_quads(tile_size), live_words]: see gs_blend_live_words;
                                    NULL: none written (a caller's memory budget for large tiles; the
                                    backward then replays every entry of a cell's evaluated prefix) */
@@ -319,8 +322,10 @@ typedef struct gs_blend_fwd_args {
                                    work counter C of SURVEY 8(d); measurement only */
   int32_t num_pairs;            /* T, the entries of sorted_gauss: tile ranges are clamped to it */
   uint32_t *pix_neval;          /* [H*W] or NULL: each pixel's evaluated entries (the work counter
-                                   E of SURVEY 8(d), and the oracle's decision-forced replay);
-                                   measurement only */
+                                   E of SURVEY 8(d), and the oracle's decision-forced replay): 1 +
+                                   the list index of the entry after which the pixel's A reached
+                                   0.995, or the length of its tile's list if it never did (entries
+                                   skipped on the way count); measurement only */
 } gs_blend_fwd_args;
 gs_status gs_blend_forward(const gs_blend_fwd_args *a, gs_stream_t stream);
 
