@@ -384,6 +384,21 @@ typedef struct gs_blend_bwd_args {
   int32_t cell_count;           /* the batch's cells (0: gs_tile_quads(tile_size), the whole tile) */
 } gs_blend_bwd_args;
 gs_status gs_blend_backward(const gs_blend_bwd_args *a, gs_stream_t stream);
+/* gs_blend_backward with the absolute screen-space gradients (AbsGS; gsplat's
+ * absgrad) beside the partials: everything above is written as there, bit for
+ * bit (the same checks, cell batches and grid), and for every (entry, group)
+ * whose slot_live flag it sets also
+ *   abs_grads[2 (G e + q) + 0] = sum_p |dL/dmu_x(p)|
+ *   abs_grads[2 (G e + q) + 1] = sum_p |dL/dmu_y(p)|
+ * over group q's pixels p, where dL/dmu(p) is pixel p's own term of
+ * pair_grads' dmu_x, dmu_y (their sum over p): the signed sum lets a large
+ * Gaussian's per-pixel gradients cancel, this one does not.  Per pixel:
+ * |dL/ds(p)| |(2 Q00 dx + (Q01+Q10) dy, (Q01+Q10) dx + 2 Q11 dy)|, (dx, dy)
+ * the forward's own offsets.  abs_grads: device [T, G, 2] fp32, 8-byte
+ * aligned; entries whose flag stays 0 are not written.  The colour pass only:
+ * the feature and distortion backwards have no absolute form.  A NULL or
+ * misaligned abs_grads: GS_ERR_INVALID_ARG before any HIP call. */
+gs_status gs_blend_backward_abs(const gs_blend_bwd_args *a, float *abs_grads, gs_stream_t stream);
 /* Diagnostic (SURVEY 8(d) lane efficiency; not on the render path): the same
  * replay as gs_blend_backward at the default tile (one batch), counting its
  * phase-A lanes.  hist: device [2][65] uint64, added to -- per replayed
@@ -716,6 +731,27 @@ gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream);
  * blend backward run in cell batches: batch b's sums are added after batch
  * b - 1's, a fixed order.  Reads vis, rects, pair_offset, g.n. */
 gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, gs_stream_t stream);
+/* The same gather over gs_blend_backward_abs' absolute partials: for every
+ * g < n, abs_sums[2g + k] = (accumulate ? abs_sums[2g + k] : 0) + the sum of
+ * abs_grads[2 (G e + q) + k] over g's slots e and the groups q slot_live
+ * flags, in gs_gather_partials' slot, group and lane order (fixed: no
+ * atomics, bitwise reproducible; cell batches are added in batch order).  A
+ * Gaussian that is invisible or has no live partial gets zeros when storing
+ * and keeps its sums when accumulating.  Run it after each batch's
+ * gs_blend_backward_abs, before slot_live is cleared for the next.  n == 0:
+ * GS_OK, nothing launched. */
+typedef struct gs_abs_gather_args {
+  int32_t n;
+  const uint8_t *vis;          /* [n] */
+  const uint32_t *rects;       /* [n] packed tile rectangles */
+  const uint32_t *pair_offset; /* [n] first slot */
+  const float *abs_grads;      /* [T, G, 2] from gs_blend_backward_abs */
+  const uint8_t *slot_live;    /* [T, G] */
+  int32_t partial_groups;      /* G: the blend backward's cell_count */
+  int32_t accumulate;          /* 0: store, 1: add to abs_sums */
+  float *abs_sums;             /* [n, 2] */
+} gs_abs_gather_args;
+gs_status gs_gather_abs_partials(const gs_abs_gather_args *a, gs_stream_t stream);
 
 /* ---- Backward of the projection, with the camera pose's gradient --------
  * gs_project_backward (every d_* of bwd is written as there, bit for bit)
@@ -855,6 +891,16 @@ gs_status gs_loss_backward(const gs_loss_args *a, gs_stream_t stream);
  * new and smaller: unaffected.  Split geometry, clone jitter, output order,
  * moment remap and counters are as above either way.
  *
+ * AbsGS rule (trailing fields too, zero: the above bit for bit).  With
+ * split_accum (the absolute statistic of gs_density_accumulate_abs) the split
+ * test reads
+ *   ga = grad_denom[i] > 0 ? split_accum[i] / grad_denom[i] : 0
+ * against split_threshold -- split = ga > split_threshold and s > split_size *
+ * scene_extent -- while the clone test keeps g against grad_threshold: large
+ * Gaussians split on the absolute gradient, which their signed per-pixel
+ * gradients cannot cancel, small ones clone on the signed one.  split_accum
+ * without grad_accum / grad_denom is GS_ERR_INVALID_ARG.
+ *
  * gs_density_accumulate adds one rendered view to those statistics, after
  * that view's backward: one launch, one thread per Gaussian, no atomics.  For
  * every g < n with vis[g] != 0, with W, H the rendered image's size,
@@ -880,6 +926,23 @@ typedef struct gs_density_stats_args {
   float *grad_accum, *denom, *max_radii; /* [n] each, read-modify-written where visible */
 } gs_density_stats_args;
 gs_status gs_density_accumulate(const gs_density_stats_args *a, gs_stream_t stream);
+/* gs_density_accumulate with the absolute statistic: one launch in place of
+ * that one (not after it).  stats' grad_accum, denom and max_radii get exactly
+ * what gs_density_accumulate gives them, bit for bit, and for the same rows
+ *   ax = (abs_sums ? abs_sums[2g]     : 0) + (g_means2d ? |g_means2d[2g]|     : 0)
+ *   ay = (abs_sums ? abs_sums[2g + 1] : 0) + (g_means2d ? |g_means2d[2g + 1]| : 0)
+ *   abs_accum[g] += sqrtf((0.5f W ax)^2 + (0.5f H ay)^2)
+ * abs_sums is what gs_gather_abs_partials leaves (the colour pass's blend;
+ * feature and distortion passes add to grad_sums only), or NULL for a frame
+ * without a blend gradient.  A row with vis[g] == 0 is neither read nor
+ * written.  Checks as gs_density_accumulate, and a NULL abs_accum with n > 0
+ * is GS_ERR_INVALID_ARG. */
+typedef struct gs_density_abs_args {
+  gs_density_stats_args stats;       /* gs_density_accumulate's arguments */
+  const float *abs_sums;             /* [n, 2], or NULL */
+  float *abs_accum;                  /* [n], read-modify-written where visible */
+} gs_density_abs_args;
+gs_status gs_density_accumulate_abs(const gs_density_abs_args *a, gs_stream_t stream);
 
 #define GS_DENSIFY_SPLIT 1
 #define GS_DENSIFY_CLONE 2
@@ -911,6 +974,9 @@ typedef struct gs_densify_args {
   const float *grad_accum, *grad_denom; /* [n] each: the gradient test reads their quotient */
   const float *max_radii;         /* [n], or NULL */
   float max_screen_radius;        /* > 0 with max_radii and GS_DENSIFY_PRUNE: drop larger unsplit originals */
+  /* AbsGS (above); both zero: split and clone read the same mean */
+  const float *split_accum;       /* [n] gs_density_accumulate_abs' abs_accum, or NULL */
+  float split_threshold;          /* the split test's threshold on split_accum / grad_denom */
 } gs_densify_args;
 size_t gs_densify_workspace_bytes(int32_t n);
 gs_status gs_densify_count(const gs_densify_args *a, gs_stream_t stream);

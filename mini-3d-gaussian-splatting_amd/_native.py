@@ -278,6 +278,7 @@ class GsDensifyArgs(C.Structure):
         ("workspace_bytes", C.c_size_t), ("counters", _vp), ("out", GsModelArrays),
         ("adam_m_out", GsModelArrays), ("adam_v_out", GsModelArrays),
         ("grad_accum", _vp), ("grad_denom", _vp), ("max_radii", _vp), ("max_screen_radius", C.c_float),
+        ("split_accum", _vp), ("split_threshold", C.c_float),
     ]
 
 
@@ -285,6 +286,17 @@ class GsDensityStatsArgs(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("image_width", C.c_int32), ("image_height", C.c_int32), ("vis", _vp), ("radii", _vp),
         ("grad_sums", _vp), ("g_means2d", _vp), ("grad_accum", _vp), ("denom", _vp), ("max_radii", _vp),
+    ]
+
+
+class GsDensityAbsArgs(C.Structure):
+    _fields_ = [("stats", GsDensityStatsArgs), ("abs_sums", _vp), ("abs_accum", _vp)]
+
+
+class GsAbsGatherArgs(C.Structure):
+    _fields_ = [
+        ("n", C.c_int32), ("vis", _vp), ("rects", _vp), ("pair_offset", _vp), ("abs_grads", _vp),
+        ("slot_live", _vp), ("partial_groups", C.c_int32), ("accumulate", C.c_int32), ("abs_sums", _vp),
     ]
 
 
@@ -336,6 +348,7 @@ EXPORTS = (
     "gs_blend_contributions", "gs_contrib_accumulate",
     "gs_blend_distortion_forward", "gs_blend_distortion_backward",
     "gs_mcmc_sample", "gs_mcmc_relocate_workspace_bytes", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize",
+    "gs_blend_backward_abs", "gs_gather_abs_partials", "gs_density_accumulate_abs",
 )
 
 _lib = None
@@ -410,13 +423,17 @@ def _declare(lib):
     lib.gs_mcmc_relocate.argtypes = [P(GsMcmcRelocateArgs), _vp]
     lib.gs_mcmc_noise.argtypes = [P(GsMcmcNoiseArgs), _vp]
     lib.gs_mcmc_regularize.argtypes = [P(GsMcmcRegularizeArgs), _vp]
+    lib.gs_blend_backward_abs.argtypes = [P(GsBlendBwdArgs), _vp, _vp]
+    lib.gs_gather_abs_partials.argtypes = [P(GsAbsGatherArgs), _vp]
+    lib.gs_density_accumulate_abs.argtypes = [P(GsDensityAbsArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
               "gs_density_accumulate", "gs_blend_features_forward", "gs_blend_features_backward", "gs_gather_feature_partials",
               "gs_blend_contributions", "gs_contrib_accumulate", "gs_blend_distortion_forward",
               "gs_blend_distortion_backward", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
-              "gs_mcmc_regularize"):
+              "gs_mcmc_regularize", "gs_blend_backward_abs", "gs_gather_abs_partials",
+              "gs_density_accumulate_abs"):
         getattr(lib, f).restype = C.c_int
 
 

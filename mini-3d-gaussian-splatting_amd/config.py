@@ -59,6 +59,13 @@ class TrainingConfig:
     # saw the Gaussian since the last densification (the quantity densify_grad_threshold is the 3DGS
     # value of); or "mcmc", the 3DGS-MCMC family (the mcmc_* fields below)
     densify_criterion: str = "xyz_grad"
+    # "screen" with AbsGS's rule (gsplat's absgrad): the split test reads the mean *absolute* screen-space
+    # gradient -- the per-pixel |dL/dmu| summed, which a large Gaussian's pixels cannot cancel -- against
+    # densify_abs_grad_threshold (0.0008: gsplat's published absgrad value); the clone test keeps the
+    # signed mean against densify_grad_threshold.  The renders then take the stage path (the same image
+    # and gradients) with the absolute-gradient blend backward
+    densify_absgrad: bool = False
+    densify_abs_grad_threshold: float = 0.0008
     prune_screen_radius: float = 0.0   # "screen": also prune Gaussians whose largest screen radius (px) exceeded it; 0 = off
     # cap opacities at 0.01 every this many iterations while densifying (0 = never); a Gaussian the
     # training has not raised above min_opacity again by the next densification is pruned there
@@ -103,6 +110,12 @@ class TrainingConfig:
         """Values no run can use (the trainer asks at setup)."""
         if self.densify_criterion not in DENSIFY_CRITERIA:
             raise ValueError(f"densify_criterion must be one of {DENSIFY_CRITERIA}, got {self.densify_criterion!r}")
+        if self.densify_absgrad and self.densify_criterion != "screen":
+            raise ValueError("densify_absgrad needs densify_criterion 'screen' (the absolute gradient is a screen-space "
+                             f"statistic), got {self.densify_criterion!r}")
+        t = float(self.densify_abs_grad_threshold)
+        if not (t >= 0.0 and t != float("inf")):
+            raise ValueError(f"densify_abs_grad_threshold must be finite and >= 0, got {self.densify_abs_grad_threshold!r}")
         s = float(self.screen_filter)
         if not (s >= 0.0 and s != float("inf")):
             raise ValueError(f"screen_filter must be a finite variance >= 0 (px^2), got {self.screen_filter!r}")

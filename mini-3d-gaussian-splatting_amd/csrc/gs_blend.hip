@@ -372,8 +372,18 @@ struct BwdStats {
   uint32_t *per_group;       // [grid][4]
 };
 
-template <bool kT16, bool kStats = false>
-__global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdStats stats = {nullptr, nullptr}) {
+// Absolute screen-space gradients (gs_blend_backward_abs; the kAbs
+// instantiations only -- the product kernel carries none of it): phase B also
+// sums, per (entry, cell), |dL/dmu_x| and |dL/dmu_y| pixel by pixel -- the
+// moments cannot give them, |.| of a linear form in (dx, dy) does not factor --
+// and writes them as a float2 beside the 40-byte partial.
+struct BwdAbs {
+  float2 *grads;  // [T, G]: (sum_p |dL/dmu_x(p)|, sum_p |dL/dmu_y(p)|), flagged by slot_live
+};
+
+template <bool kT16, bool kStats = false, bool kAbs = false>
+__global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdStats stats = {nullptr, nullptr},
+                                                     BwdAbs absg = {nullptr}) {
   __shared__ float2 s_dc[kBwdGroup][kBwdRow];  // per group entry and pixel: (dop, c)
   __shared__ uint32_t s_hist[kStats ? 2 * 65 : 1];
   uint32_t n_rep = 0, n_rep32 = 0, sum_run = 0, sum_con = 0;  // (kStats)
@@ -513,6 +523,8 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
       const bool small_y = q00 < 4.f * (q00 * q11 - q01h * q01h);  // Sigma_yy = q00 / det < 4
       float S0 = 0.f, Soy = 0.f, Soyy = 0.f, g5 = 0.f, g6 = 0.f, g7 = 0.f, g8 = 0.f, g9 = 0.f;
       float rc = 0.f;
+      float ax = 0.f, ay = 0.f;  // (kAbs) sums of |ds| |d s / d mu| over the column's pixels
+      const float qxx = 2.f * q00 * bx, qxy = qo * bx, q11x2 = 2.f * q11;  // (kAbs)
       auto moments = [&](auto recenter_tag) {
         constexpr bool kRec = decltype(recenter_tag)::value;
         if constexpr (kRec)
@@ -540,6 +552,19 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
             Soyy = __builtin_fmaf(ds, (float)(r * r), Soyy);
           }
           if constexpr (kMasked) g5 += dop;
+          if constexpr (kAbs) {
+            // the pixel's own gradient, not through the moments: ds/dmu =
+            // -(2 q00 dx + qo dy, qo dx + 2 q11 dy) at the forward's dy; no
+            // recentring, nothing cancels in a sum of absolute values
+            // (the empty asm keeps the row's terms in the row: hoisted out of the
+            // unrolled loop, eight rows of them cost 17 VGPRs and a wave per SIMD)
+            float yr = (float)(y0 + r);
+            asm volatile("" : "+v"(yr));
+            const float dyr = yr - ia.y;
+            const float ads = fabsf(ds);
+            ax = __builtin_fmaf(ads, fabsf(__builtin_fmaf(qo, dyr, qxx)), ax);
+            ay = __builtin_fmaf(ads, fabsf(__builtin_fmaf(q11x2, dyr, qxy)), ay);
+          }
           g6 = __builtin_fmaf(pg.x, cw, g6);
           g7 = __builtin_fmaf(pg.y, cw, g7);
           g8 = __builtin_fmaf(pg.z, cw, g8);
@@ -558,6 +583,11 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
       float g4 = __builtin_fmaf(by, __builtin_fmaf(by, S0, 2.f * Soy), Soyy);
       Sx = oct_sum(Sx); Sy = oct_sum(Sy); g2 = oct_sum(g2); g3 = oct_sum(g3); g4 = oct_sum(g4);
       g5 = oct_sum(g5); g6 = oct_sum(g6); g7 = oct_sum(g7); g8 = oct_sum(g8); g9 = oct_sum(g9);
+      if constexpr (kAbs) {
+        const float ah = fabsf(hop);  // dL/ds = hop dop: scaled once, as the moments are
+        ax = oct_sum(ax * ah);
+        ay = oct_sum(ay * ah);
+      }
       if (col == 0) {
         // dmu = -(2 q00 Sx + qo Sy, qo Sx + 2 q11 Sy)
         const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
@@ -567,6 +597,7 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
         *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2, g3};
         *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, g6, g7};
         *reinterpret_cast<f2_u8 *>(out + 8) = f2_u8{g8, g9};
+        if constexpr (kAbs) absg.grads[sq] = make_float2(ax, ay);
         a.slot_live[sq] = 1;
       }
     }
@@ -724,6 +755,44 @@ bool tiles_match(const gs_camera &c, int tiles_x, int tiles_y) {
   return tiles_x == (int)div_up(c.image_width, c.tile_size) && tiles_y == (int)div_up(c.image_height, c.tile_size);
 }
 
+// gs_blend_backward's checks, cell batch and launch; abs_grads: NULL, or the
+// [T, G, 2] buffer of gs_blend_backward_abs (the kAbs instantiations)
+gs_status blend_backward(const gs_blend_bwd_args *a, float *abs_grads, const char *what, gs_stream_t stream) {
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, what);
+  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", what);
+  if (!a->ranges || !a->sorted_gauss || !a->records || !a->image || !a->alpha || !a->depth || !a->pix_flags ||
+      !a->cell_neval || !a->g_image ||
+      !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", what);
+  if (a->num_pairs < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs", what);
+  const int cells = cells_per_tile(a->cam.tile_size);
+  gs_blend_bwd_args b = *a;
+  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
+  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
+                "[0, gs_tile_quads(tile_size))", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int num_tiles = b.tiles_x * b.tiles_y;
+  if (num_tiles <= 0) return GS_OK;
+  const long long blocks = (long long)div_up(num_tiles, 8) * 8LL * b.cell_count;
+  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", what);
+  const bool t16 = b.cam.tile_size == GS_DEFAULT_TILE && b.cell_count == cells;
+  if (abs_grads) {
+    const BwdAbs ab{reinterpret_cast<float2 *>(abs_grads)};
+    if (t16)
+      k_blend_bwd<true, false, true><<<(unsigned)blocks, kWave, 0, s>>>(b, BwdStats{nullptr, nullptr}, ab);
+    else
+      k_blend_bwd<false, false, true><<<(unsigned)blocks, kWave, 0, s>>>(b, BwdStats{nullptr, nullptr}, ab);
+  } else if (t16) {
+    k_blend_bwd<true><<<(unsigned)blocks, kWave, 0, s>>>(b);
+  } else {
+    k_blend_bwd<false><<<(unsigned)blocks, kWave, 0, s>>>(b);
+  }
+  return gs_internal_check_launch(what);
+}
+
 }  // namespace
 
 // ============================================================ C ABI =======
@@ -768,31 +837,14 @@ gs_status gs_blend_forward(const gs_blend_fwd_args *a, gs_stream_t stream) {
 }
 
 gs_status gs_blend_backward(const gs_blend_bwd_args *a, gs_stream_t stream) {
-  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_blend_backward");
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, "gs_blend_backward");
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", "gs_blend_backward");
-  if (!a->ranges || !a->sorted_gauss || !a->records || !a->image || !a->alpha || !a->depth || !a->pix_flags ||
-      !a->cell_neval || !a->g_image ||
-      !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", "gs_blend_backward");
-  if (a->num_pairs < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs", "gs_blend_backward");
-  const int cells = cells_per_tile(a->cam.tile_size);
-  gs_blend_bwd_args b = *a;
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
-                "[0, gs_tile_quads(tile_size))", "gs_blend_backward");
-  hipStream_t s = (hipStream_t)stream;
-  const int num_tiles = b.tiles_x * b.tiles_y;
-  if (num_tiles <= 0) return GS_OK;
-  const long long blocks = (long long)div_up(num_tiles, 8) * 8LL * b.cell_count;
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", "gs_blend_backward");
-  if (b.cam.tile_size == GS_DEFAULT_TILE && b.cell_count == cells)
-    k_blend_bwd<true><<<(unsigned)blocks, kWave, 0, s>>>(b);
-  else
-    k_blend_bwd<false><<<(unsigned)blocks, kWave, 0, s>>>(b);
-  return gs_internal_check_launch("gs_blend_backward");
+  return blend_backward(a, nullptr, "gs_blend_backward", stream);
+}
+
+gs_status gs_blend_backward_abs(const gs_blend_bwd_args *a, float *abs_grads, gs_stream_t stream) {
+  if (!abs_grads || (reinterpret_cast<uintptr_t>(abs_grads) & 7u))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: abs_grads must be an 8-byte aligned [T, G, 2] buffer",
+                            "gs_blend_backward_abs");
+  return blend_backward(a, abs_grads, "gs_blend_backward_abs", stream);
 }
 
 int64_t gs_blend_backward_groups(int32_t tiles_x, int32_t tiles_y, int32_t cell_count) {

@@ -11,7 +11,9 @@
 //
 // gs_density_accumulate (k_density_accumulate) keeps the screen-space
 // statistics the classification can read instead of |xyz_grad|: one streaming
-// launch after a rendered view's backward.
+// launch after a rendered view's backward.  gs_density_accumulate_abs
+// (k_density_accumulate_abs) is that launch with the absolute-gradient
+// statistic (AbsGS) beside them, which the split test can read (split_accum).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -50,7 +52,12 @@ __device__ Cls classify(const gs_densify_args &a, int i) {
       gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);  // .norm(dim=-1)
     }
     const bool hot = gn > a.grad_threshold;
-    split = (a.flags & GS_DENSIFY_SPLIT) && hot && c.smean > a.split_size * a.scene_extent;   // :137
+    bool hot_split = hot;
+    if (a.split_accum) {  // AbsGS: the split test on the mean absolute gradient, the clone test as it was
+      const float d = a.grad_denom[i];
+      hot_split = (d > 0.f ? a.split_accum[i] / d : 0.f) > a.split_threshold;
+    }
+    split = (a.flags & GS_DENSIFY_SPLIT) && hot_split && c.smean > a.split_size * a.scene_extent;   // :137
     clone = (a.flags & GS_DENSIFY_CLONE) && hot && c.smean < a.clone_size * a.scene_extent;   // :166
   }
   // children: clamp(logit(get_opacity), -6, 6) (:150)
@@ -207,6 +214,8 @@ gs_status check_args(const gs_densify_args *a, const char *what) {
   if (a->n < 0 || a->rest_floats < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad size", what);
   if (a->grad_accum && (a->xyz_grad || !a->grad_denom))
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: grad_accum needs grad_denom and excludes xyz_grad", what);
+  if (a->split_accum && (!a->grad_accum || !a->grad_denom))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: split_accum needs grad_accum and grad_denom", what);
   if (a->n > 0 && (!a->in.xyz || !a->in.features_dc || !a->in.scaling || !a->in.rotation || !a->in.opacity ||
                    (a->rest_floats > 0 && !a->in.features_rest) || !a->counters || !a->workspace ||
                    a->workspace_bytes < gs_densify_workspace_bytes(a->n)))
@@ -218,9 +227,7 @@ gs_status check_args(const gs_densify_args *a, const char *what) {
 // 1 B (vis) per Gaussian; per visible one 8 B of its 40 B grad_sums row (the
 // row's cache lines move whole), 8 B g_means2d, 4 B radius, and the three
 // statistics read and written (24 B): ~70 B of traffic.
-__global__ __launch_bounds__(kB) void k_density_accumulate(gs_density_stats_args a, float sx, float sy) {
-  const int g = blockIdx.x * kB + threadIdx.x;
-  if (g >= a.n || !a.vis[g]) return;
+__device__ __forceinline__ void density_accumulate_one(const gs_density_stats_args &a, int g, float sx, float sy) {
   float gx = 0.f, gy = 0.f;
   if (a.grad_sums) {
     const float2 s = *reinterpret_cast<const float2 *>(a.grad_sums + (size_t)g * GS_PAIR_GRAD_FLOATS);
@@ -238,20 +245,70 @@ __global__ __launch_bounds__(kB) void k_density_accumulate(gs_density_stats_args
   a.max_radii[g] = fmaxf(a.max_radii[g], a.radii[g]);
 }
 
+__global__ __launch_bounds__(kB) void k_density_accumulate(gs_density_stats_args a, float sx, float sy) {
+  const int g = blockIdx.x * kB + threadIdx.x;
+  if (g >= a.n || !a.vis[g]) return;
+  density_accumulate_one(a, g, sx, sy);
+}
+
+// gs_density_accumulate_abs: the three statistics as above (the same code),
+// and the absolute statistic from the abs gather's sums: 8 B more read and
+// 8 B read and written per visible Gaussian.
+__global__ __launch_bounds__(kB) void k_density_accumulate_abs(gs_density_abs_args a, float sx, float sy) {
+  const int g = blockIdx.x * kB + threadIdx.x;
+  if (g >= a.stats.n || !a.stats.vis[g]) return;
+  density_accumulate_one(a.stats, g, sx, sy);
+  float ax = 0.f, ay = 0.f;
+  if (a.abs_sums) {
+    const float2 s = reinterpret_cast<const float2 *>(a.abs_sums)[g];
+    ax = s.x;
+    ay = s.y;
+  }
+  if (a.stats.g_means2d) {
+    const float2 m = reinterpret_cast<const float2 *>(a.stats.g_means2d)[g];
+    ax += fabsf(m.x);
+    ay += fabsf(m.y);
+  }
+  const float nx = sx * ax, ny = sy * ay;
+  a.abs_accum[g] += sqrtf(nx * nx + ny * ny);
+}
+
 }  // namespace
 
 extern "C" size_t gs_densify_workspace_bytes(int32_t n) {
   return n > 0 ? sizeof(uint32_t) * 3 * (size_t)nblocks(n) : 0;
 }
 
-extern "C" gs_status gs_density_accumulate(const gs_density_stats_args *a, gs_stream_t stream) {
-  static const char *what = "gs_density_accumulate";
-  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+// gs_density_accumulate's argument checks; GS_OK with *launch = false: n == 0
+static gs_status check_density_stats(const gs_density_stats_args *a, const char *what, bool *launch) {
+  *launch = false;
   if (a->n < 0 || a->image_width <= 0 || a->image_height <= 0)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad size (n >= 0, image_width and image_height > 0)", what);
   if (a->n == 0) return GS_OK;
   if (!a->vis || !a->radii || !a->grad_accum || !a->denom || !a->max_radii)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null vis, radii, grad_accum, denom or max_radii", what);
+  *launch = true;
+  return GS_OK;
+}
+
+extern "C" gs_status gs_density_accumulate_abs(const gs_density_abs_args *a, gs_stream_t stream) {
+  static const char *what = "gs_density_accumulate_abs";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  bool launch;
+  if (gs_status st = check_density_stats(&a->stats, what, &launch)) return st;
+  if (!launch) return GS_OK;
+  if (!a->abs_accum) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null abs_accum", what);
+  k_density_accumulate_abs<<<nblocks(a->stats.n), kB, 0, (hipStream_t)stream>>>(
+      *a, 0.5f * (float)a->stats.image_width, 0.5f * (float)a->stats.image_height);
+  return gs_internal_check_launch(what);
+}
+
+extern "C" gs_status gs_density_accumulate(const gs_density_stats_args *a, gs_stream_t stream) {
+  static const char *what = "gs_density_accumulate";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  bool launch;
+  if (gs_status st = check_density_stats(a, what, &launch)) return st;
+  if (!launch) return GS_OK;
   k_density_accumulate<<<nblocks(a->n), kB, 0, (hipStream_t)stream>>>(*a, 0.5f * (float)a->image_width,
                                                                        0.5f * (float)a->image_height);
   return gs_internal_check_launch(what);

@@ -1,6 +1,7 @@
 // gs_project.hip -- the per-Gaussian ends of the render path:
 //   k_project_fwd     renderer.py:117-220   projection, 2D cov, conic, radius, culling
 //   k_gather_slots    the sum of a Gaussian's gradient partials (k_blend_bwd's slots)
+//   k_gather_abs      the same walk over the absolute-gradient partials (gs_blend_backward_abs)
 //   k_project_bwd     autograd of :117-200  (+ gaussian_model.py:200-207 on the raw path),
 //                     with its camera-pose (k_pose_reduce) and fused-Adam forms
 // (src/core/renderer.py of the reference.)
@@ -441,6 +442,70 @@ __global__ __launch_bounds__(kBlock) void k_gather_slots(gs_project_bwd_args a, 
     } else {
 #pragma unroll
       for (int k = 0; k < kF2; ++k) out[k] = acc[k];
+    }
+  }
+}
+
+// The absolute-gradient partials of gs_blend_backward_abs ([T, ng] float2,
+// flagged by the same slot_live) summed per Gaussian: k_gather_slots' lanes
+// and order -- lane (h, q) of g adds the groups q, q + QL, ... of its slots h,
+// h + HL, ... in that order, then the lane sums in the fixed DPP order -- so
+// the sums are bitwise reproducible.  8 B per partial, a fifth of
+// k_gather_slots' bytes, but latency decides as there: flags and partials of
+// kGatherNB slots per round trip (one slot at a time took 97.8 us at C3, as
+// long as k_gather_slots).
+template <int QL, int HL>
+__global__ __launch_bounds__(kBlock) void k_gather_abs(gs_abs_gather_args a) {
+  constexpr int LPG = QL * HL;
+  static_assert(LPG == 2 || LPG == 4 || LPG == 8, "lanes per Gaussian");
+  const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const int g = (int)(t / LPG);
+  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
+  const bool valid = g < a.n;
+  const uint32_t gi = valid ? (uint32_t)g : 0u;
+  const uint32_t visb = a.vis[gi];
+  int tx0, tx1, ty0, ty1;
+  unpack_rect(a.rects, gi, tx0, tx1, ty0, ty1);
+  const size_t off = a.pair_offset[gi];
+  const uint32_t cnt = (valid && visb) ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
+  const uint32_t ng = (uint32_t)a.partial_groups;
+  float sx = 0.f, sy = 0.f;
+  for (uint32_t qc = (uint32_t)q; cnt > (uint32_t)h && qc < ng; qc += QL) {
+    const uint8_t *flag = a.slot_live + off * ng + qc;  // (slot e, group qc) at flag[ng e]
+    const float2 *part = reinterpret_cast<const float2 *>(a.abs_grads) + off * ng + qc;
+    for (uint32_t e0 = (uint32_t)h; e0 < cnt; e0 += kGatherNB * HL) {
+      // the batch's flags and partials in one round trip: unconditional loads
+      // (past the end the clamped index re-reads slot e0; a dead partial is
+      // read -- 8 B of whatever the buffer holds -- and never used), masked after
+      uint32_t f[kGatherNB];
+      float2 v[kGatherNB];
+#pragma unroll
+      for (int i = 0; i < kGatherNB; ++i) {
+        const uint32_t e = e0 + HL * i;
+        const size_t at = (size_t)ng * (e < cnt ? e : e0);
+        f[i] = flag[at];
+        v[i] = part[at];
+      }
+      uint32_t fm = 0;
+#pragma unroll
+      for (int i = 0; i < kGatherNB; ++i) fm |= (e0 + HL * i < cnt && f[i]) ? 1u << i : 0u;
+#pragma unroll
+      for (int i = 0; i < kGatherNB; ++i) {
+        if (!((fm >> i) & 1u)) continue;
+        sx += v[i].x;
+        sy += v[i].y;
+      }
+    }
+  }
+  sx = lanes_sum<LPG>(sx);
+  sy = lanes_sum<LPG>(sy);
+  if ((t % LPG) == 0 && valid) {
+    float2 *out = reinterpret_cast<float2 *>(a.abs_sums) + g;
+    if (a.accumulate) {
+      const float2 o = *out;
+      *out = make_float2(o.x + sx, o.y + sy);
+    } else {
+      *out = make_float2(sx, sy);
     }
   }
 }
@@ -1077,6 +1142,25 @@ gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, g
       a->partial_groups < 1)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer or partial_groups < 1", "gs_gather_partials");
   return launch_gather(a, accumulate, (hipStream_t)stream);
+}
+
+gs_status gs_gather_abs_partials(const gs_abs_gather_args *a, gs_stream_t stream) {
+  static const char *what = "gs_gather_abs_partials";
+  if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
+  if (a->n < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad n", what);
+  if (a->n == 0) return GS_OK;
+  if (!a->abs_grads || !a->slot_live || !a->abs_sums || !a->vis || !a->rects || !a->pair_offset ||
+      a->partial_groups < 1)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer or partial_groups < 1", what);
+  hipStream_t s = (hipStream_t)stream;
+  // (k_gather_slots' lanes per Gaussian for the same partial_groups)
+  if (a->partial_groups == 1)
+    k_gather_abs<1, kGatherHL1><<<div_up((long long)kGatherHL1 * a->n, kBlock), kBlock, 0, s>>>(*a);
+  else if (a->partial_groups == 2)
+    k_gather_abs<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  else
+    k_gather_abs<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  return gs_internal_check_launch(what);
 }
 
 gs_status gs_project_backward(const gs_project_bwd_args *a, gs_stream_t stream) {

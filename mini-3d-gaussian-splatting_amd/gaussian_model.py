@@ -60,7 +60,9 @@ class GaussianModel(nn.Module):
         self.register_buffer("max_radii2D", torch.zeros(0))
         # the statistics the renderer fills (render(..., density_stats=)) and the "screen"
         # densification reads; zeros of the model's size wherever the three buffers above are re-made
-        self.density_stats = DensityStats(0, self._xyz.device)
+        # (with config.densify_absgrad they keep the absolute gradient too: DensityStats.abs_accum)
+        self.density_abs_grad = bool(getattr(config, "densify_absgrad", False))
+        self.density_stats = DensityStats(0, self._xyz.device, self.density_abs_grad)
         self._contribution_stats = None  # (made on first use: see contribution_stats)
         self.scaling_activation = torch.exp
         self.scaling_inverse_activation = torch.log
@@ -71,7 +73,7 @@ class GaussianModel(nn.Module):
         """Module.to / .cuda: the statistics follow the parameters (as zeros)."""
         out = super()._apply(fn, *args, **kwargs)
         if self.density_stats.device != self._xyz.device:
-            self.density_stats = DensityStats(self.get_num_points(), self._xyz.device)
+            self.density_stats = DensityStats(self.get_num_points(), self._xyz.device, self.density_abs_grad)
         if self._contribution_stats is not None and self._contribution_stats.device != self._xyz.device:
             self._contribution_stats = None
         return out
@@ -105,7 +107,7 @@ class GaussianModel(nn.Module):
         self.xyz_gradient_accum = torch.zeros(n, 3, device=dev)
         self.denom = torch.zeros(n, 1, device=dev)
         self.max_radii2D = torch.zeros(n, device=dev)
-        self.density_stats = DensityStats(n, dev)
+        self.density_stats = DensityStats(n, dev, self.density_abs_grad)
         self._contribution_stats = None
 
     @torch.no_grad()
@@ -219,7 +221,7 @@ class GaussianModel(nn.Module):
                           optimizer: Optional[torch.optim.Optimizer] = None, seed: Optional[int] = None,
                           split: bool = True, clone: bool = True, prune: bool = True,
                           xyz_grad: Optional[torch.Tensor] = None, stats: Optional[DensityStats] = None,
-                          max_screen_radius: float = 0.0) -> dict:
+                          max_screen_radius: float = 0.0, abs_grad_threshold: Optional[float] = None) -> dict:
         """Split large / clone small high-gradient Gaussians, then drop those
         with opacity <= min_opacity, in one GPU pass (semantics in
         include/gsplat_mi355x.h, "Densification").  With `optimizer`, its
@@ -228,7 +230,10 @@ class GaussianModel(nn.Module):
         stats: a DensityStats of the model's size: the gradient test reads its
         mean screen-space gradient instead of |xyz_grad| (not both), and, with
         prune and max_screen_radius > 0, unsplit Gaussians whose max_radii
-        exceed it are dropped too."""
+        exceed it are dropped too.
+        abs_grad_threshold: with stats that keep abs_accum, AbsGS's rule: the
+        split test reads the mean absolute gradient against this threshold,
+        the clone test the signed mean against grad_threshold."""
         params = self.parameter_list()
         n, dev = self.get_num_points(), self._xyz.device
         if stats is not None:
@@ -236,6 +241,8 @@ class GaussianModel(nn.Module):
                 raise ValueError("densify_and_prune takes stats or xyz_grad, not both")
             if stats.n != n or stats.device != dev:
                 raise ValueError(f"stats holds {stats.n} Gaussians on {stats.device}, the model {n} on {dev}")
+        if abs_grad_threshold is not None and (stats is None or stats.abs_accum is None):
+            raise ValueError("abs_grad_threshold needs stats made with DensityStats(n, device, abs_grad=True)")
         grad = None if stats is not None else (xyz_grad if xyz_grad is not None else self._xyz.grad)
         for p in params:
             if not (p.is_cuda and p.is_contiguous()):
@@ -267,6 +274,8 @@ class GaussianModel(nn.Module):
         if stats is not None:
             a.grad_accum, a.grad_denom = N.ptr(stats.grad_accum), N.ptr(stats.denom)
             a.max_radii, a.max_screen_radius = N.ptr(stats.max_radii), float(max_screen_radius)
+            if abs_grad_threshold is not None:
+                a.split_accum, a.split_threshold = N.ptr(stats.abs_accum), float(abs_grad_threshold)
         stream = N.stream_ptr()
         N.check(lib.gs_densify_count(C.byref(a), stream), "gs_densify_count")
         kept, nsplit, ncl, n_out = (int(v) for v in counters.tolist())

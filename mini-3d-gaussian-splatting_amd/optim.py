@@ -252,7 +252,9 @@ class DensityController:
     the prune.  dist: the trainer's process group module when data parallel:
     every rank has seen other views, so the statistics are all-reduced right
     before (SUM of grad_accum and denom, MAX of max_radii) and every rank
-    takes the same decisions."""
+    takes the same decisions.  With config.densify_absgrad the split test
+    reads the statistics' absolute gradient (abs_accum, all-reduced with SUM
+    beside the others) against config.densify_abs_grad_threshold."""
 
     def __init__(self, config):
         self.config = config
@@ -271,7 +273,11 @@ class DensityController:
                 dist.all_reduce(stats.grad_accum, op=dist.ReduceOp.SUM)
                 dist.all_reduce(stats.denom, op=dist.ReduceOp.SUM)
                 dist.all_reduce(stats.max_radii, op=dist.ReduceOp.MAX)
+                if stats.abs_accum is not None:
+                    dist.all_reduce(stats.abs_accum, op=dist.ReduceOp.SUM)
             kw = {"stats": stats, "max_screen_radius": float(getattr(c, "prune_screen_radius", 0.0))}
+            if getattr(c, "densify_absgrad", False):
+                kw["abs_grad_threshold"] = float(c.densify_abs_grad_threshold)
         return gaussians.densify_and_prune(c.densify_grad_threshold, scene_extent,
                                            getattr(c, "min_opacity", 0.01), optimizer=optimizer,
                                            seed=0x5EED0000 + iteration, **kw)

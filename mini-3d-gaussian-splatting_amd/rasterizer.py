@@ -303,13 +303,24 @@ class DensityStats:
     add that view to them at the end of its backward (gs_density_accumulate,
     on the backward's stream).  No backward, no statistics: a forward under
     torch.no_grad(), or one whose backward never runs, adds nothing; a second
-    backward of the same frame (retain_graph) adds the view a second time."""
-    __slots__ = ("n", "grad_accum", "denom", "max_radii")
+    backward of the same frame (retain_graph) adds the view a second time.
 
-    def __init__(self, n: int, device):
+    abs_grad=True: a fourth tensor, abs_accum (else None) -- the same sum with
+    the absolute per-pixel gradients, sum_p |dL/dmu_x(p)| and sum_p |dL/dmu_y(p)|
+    in place of the signed sums (AbsGS; gsplat's absgrad), which a large
+    Gaussian's pixels cannot cancel.  Such a render takes the stage path (the
+    same outputs and gradients, bit for bit), its blend backward is
+    gs_blend_backward_abs and its last launch gs_density_accumulate_abs.  The
+    absolute statistic covers the colour pass (and |the caller's cotangent on
+    viewspace_points|): a feature image's or a distortion map's gradient adds
+    to the signed sums only."""
+    __slots__ = ("n", "grad_accum", "denom", "max_radii", "abs_accum")
+
+    def __init__(self, n: int, device, abs_grad: bool = False):
         self.n = int(n)
         self.grad_accum, self.denom, self.max_radii = (
             torch.zeros((self.n,), dtype=torch.float32, device=device) for _ in range(3))
+        self.abs_accum = torch.zeros((self.n,), dtype=torch.float32, device=device) if abs_grad else None
 
     @property
     def device(self) -> torch.device:
@@ -318,11 +329,20 @@ class DensityStats:
     def reset(self) -> None:
         for t in (self.grad_accum, self.denom, self.max_radii):
             t.zero_()
+        if self.abs_accum is not None:
+            self.abs_accum.zero_()
 
     def mean_grad(self) -> torch.Tensor:
         """grad_accum / denom, 0 where no view saw the Gaussian."""
         seen = self.denom > 0
         return torch.where(seen, self.grad_accum / self.denom.clamp_min(1.0), torch.zeros_like(self.grad_accum))
+
+    def mean_abs_grad(self) -> torch.Tensor:
+        """abs_accum / denom, 0 where no view saw the Gaussian (abs_grad=True only)."""
+        if self.abs_accum is None:
+            raise ValueError("these DensityStats keep no absolute gradients: DensityStats(n, device, abs_grad=True)")
+        seen = self.denom > 0
+        return torch.where(seen, self.abs_accum / self.denom.clamp_min(1.0), torch.zeros_like(self.abs_accum))
 
 
 def _check_density_stats(stats, n: int, dev) -> None:
@@ -330,22 +350,35 @@ def _check_density_stats(stats, n: int, dev) -> None:
         raise TypeError(f"density_stats must be a DensityStats, got {type(stats).__name__}")
     if stats.n != n:
         raise ValueError(f"density_stats holds {stats.n} Gaussians, the render {n}")
-    for name in ("grad_accum", "denom", "max_radii"):
+    for name in ("grad_accum", "denom", "max_radii", "abs_accum"):
         t = getattr(stats, name)
+        if t is None and name == "abs_accum":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"density_stats.{name} must be a contiguous fp32 [{n}] tensor on {dev}, got "
+                             f"{type(t).__name__}")
         if tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"density_stats.{name} must be a contiguous fp32 [{n}] tensor on {dev}, got "
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
 
 
-def _accumulate_density(lib, cam: CameraParams, stats, n: int, vis, radii, grad_sums, g_means2d, s) -> None:
+def _accumulate_density(lib, cam: CameraParams, stats, n: int, vis, radii, grad_sums, g_means2d, s,
+                        abs_sums=None) -> None:
     """One gs_density_accumulate: this view added to `stats` (the last launch
     of its backward).  grad_sums: the address of the [n, 10] sums the
-    projection backward read, or None for a frame without a blend gradient."""
+    projection backward read, or None for a frame without a blend gradient.
+    Statistics with abs_accum: one gs_density_accumulate_abs in its place;
+    abs_sums: the [n, 2] sums of gs_gather_abs_partials, or None (no pixel
+    cotangent: the view and its radii still count)."""
     if stats is None or n == 0:
         return
     a = N.GsDensityStatsArgs(n, int(cam.image_width), int(cam.image_height), N.ptr(vis), N.ptr(radii),
                              grad_sums, N.ptr(g_means2d), N.ptr(stats.grad_accum), N.ptr(stats.denom),
                              N.ptr(stats.max_radii))
+    if stats.abs_accum is not None:
+        aa = N.GsDensityAbsArgs(a, N.ptr(abs_sums) or None, N.ptr(stats.abs_accum))
+        N.check(lib.gs_density_accumulate_abs(C.byref(aa), s), "gs_density_accumulate_abs")
+        return
     N.check(lib.gs_density_accumulate(C.byref(a), s), "gs_density_accumulate")
 
 
@@ -1172,7 +1205,10 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     f32 = torch.float32
     s = _stream()
     cs = cam.to_struct()
-    pair_grads = slot_live = None
+    pair_grads = slot_live = abs_sums = None
+    # (statistics with abs_accum: the blend backward also writes the absolute partials, summed
+    # per Gaussian right after each batch -- before the flags are cleared or another pass sets its own)
+    want_abs = density is not None and density[0].abs_accum is not None
     pixel_grads = g_image is not None or g_alpha is not None or g_depth is not None
     if fr.M > 0 and fr.T > 0 and pixel_grads:
         g_image, g_alpha, g_depth, image, alpha, depth = _pixel_cotangents(cam, g_image, g_alpha, g_depth, outputs,
@@ -1197,6 +1233,20 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                               N.ptr(fr.pix_flags), N.ptr(fr.cell_neval), N.ptr(g_image), N.ptr(g_alpha), N.ptr(g_depth), N.ptr(fr.live_bits),
                               0 if fr.live_bits is None else fr.live_bits.shape[1], N.ptr(pair_grads),
                               N.ptr(slot_live), fr.T, 0, 0)
+        if want_abs:
+            abs_grads = torch.empty((fr.T * G, 2), dtype=f32, device=dev)
+            abs_sums = torch.empty((n, 2), dtype=f32, device=dev)
+            aga = N.GsAbsGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(abs_grads),
+                                    N.ptr(slot_live), G, 0, N.ptr(abs_sums))
+
+        def blend_backward(batch: int) -> None:
+            if not want_abs:
+                N.check(lib.gs_blend_backward(C.byref(ba), s), "gs_blend_backward")
+                return
+            N.check(lib.gs_blend_backward_abs(C.byref(ba), N.ptr(abs_grads), s), "gs_blend_backward_abs")
+            aga.partial_groups, aga.accumulate = ba.cell_count or G, 1 if batch else 0
+            N.check(lib.gs_gather_abs_partials(C.byref(aga), s), "gs_gather_abs_partials")
+
         if G < cam.groups:
             batch_sums = torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
             ga = N.GsProjectBwdArgs()
@@ -1208,11 +1258,11 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
                 ga.partial_groups = ba.cell_count
                 if b:
                     slot_live.zero_()
-                N.check(lib.gs_blend_backward(C.byref(ba), s), "gs_blend_backward")
+                blend_backward(b)
                 N.check(lib.gs_gather_partials(C.byref(ga), 1 if b else 0, s), "gs_gather_partials")
         else:
             StageTimer.mark("blend_bwd")
-            N.check(lib.gs_blend_backward(C.byref(ba), s), "gs_blend_backward")
+            blend_backward(0)
     grads, rows_ready, chunks = _grad_buffers(out, n, cov3d is None, sh_degree, dev)
     d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = grads
     gm = None if g_means2d is None else g_means2d.contiguous()
@@ -1242,7 +1292,8 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     StageTimer.mark("project_bwd")
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
     if density is not None:
-        _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], N.ptr(grad_sums) or None, gm, s)
+        _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], N.ptr(grad_sums) or None, gm, s,
+                            abs_sums)
     StageTimer.mark("~end_bwd")
     return grads
 
@@ -1597,14 +1648,16 @@ class RasterizeGaussians(torch.autograd.Function):
         # contribution pass runs at the end of this forward
         # distort: a _DistortionPass: the stage path too, and an eighth output, the distortion map
         # density_stats: a DensityStats this frame's backward adds the view to (it needs the
-        # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape)
+        # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape);
+        # with abs_accum the stage path too: its backward is gs_blend_backward_abs
         # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
         # Gaussians' device, given only to receive its gradient -- the forward
         # reads the pose from `cam`, whose values are the same
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
             need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]),
-            stage_path=contrib is not None or distort is not None)
+            stage_path=contrib is not None or distort is not None or
+            (density_stats is not None and density_stats.abs_accum is not None))
         dist_out = () if distort is None else (_distortion_forward(cam, fr, int(xyz.shape[0]), distort, xyz.device),)
         if contrib is not None:
             _contribution_pass(cam, fr, int(xyz.shape[0]), contrib, xyz.device)
@@ -1681,6 +1734,11 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     backward of this render ends with one gs_density_accumulate that adds the
     view to it (checked here, before any launch; see DensityStats for what a
     missing or repeated backward means).  Without it the launches are the same.
+    DensityStats(abs_grad=True) take the stage path (the same outputs and
+    gradients, bit for bit) and also accumulate the absolute screen-space
+    gradient of the colour pass, abs_accum (gs_blend_backward_abs,
+    gs_gather_abs_partials, gs_density_accumulate_abs in place of the signed
+    launch); feature and distortion passes add to the signed sums only.
     features: optional floating-point [N, C] tensor on the Gaussians' device,
     C in 1..GS_MAX_FEATURE_CHANNELS: an eighth output follows the seven, the
     feature image [C, H, W] fp32 = sum_i c_i features[g_i] per pixel with the

@@ -204,7 +204,12 @@ class GaussianRenderer:
         backward, no statistics: a render under torch.no_grad(), or one whose
         backward never runs, adds nothing; backward twice (retain_graph) adds
         the view twice.  A size, device, dtype or layout mismatch is a
-        ValueError before anything is launched.
+        ValueError before anything is launched.  DensityStats(n, device,
+        abs_grad=True) also accumulate the absolute screen-space gradient
+        (AbsGS): per visible Gaussian the same norm of sum_p |dL/dmu(p)| over
+        the colour pass's pixels plus |the cotangent on viewspace_points|.
+        The frame then takes the stage path (the same bits); a feature image
+        or a distortion map adds its gradient to the signed statistic only.
         features: optional floating-point [N, C] per-Gaussian values
         (normals, embeddings, positions, ...) on the Gaussians' device.  The
         result then also holds "features" [C, H, W] fp32: each pixel's

@@ -7,7 +7,8 @@ Gaussian gradients], learning-rate schedule, FusedAdam step, and density
 control every densify_interval iterations inside [densify_from_iter,
 densify_until_iter] (optimizer.py:34-141) -- on |dL/dxyz| of the iteration's
 view, or with densify_criterion = "screen" on the 3DGS statistics every
-render's backward adds to gaussians.density_stats (then also
+render's backward adds to gaussians.density_stats (with densify_absgrad the
+absolute gradient among them, which the split test then reads; then also
 prune_screen_radius and, every opacity_reset_interval iterations, the 3DGS
 opacity reset), or with densify_criterion = "mcmc" the 3DGS-MCMC family
 (_mcmc_update: regularisers, relocation and capped growth in place of split /

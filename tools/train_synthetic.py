@@ -3,7 +3,8 @@ offline): a Blender-format scene whose ground truth is rendered from a known
 Gaussian set at 800x800, then the full GaussianTrainer loop from a random
 init.  Prints one JSON line: iterations/s, test PSNR, Gaussian count.
     python tools/train_synthetic.py [--iters 7000] [--views 100] [--size 800]
-        [--criterion xyz_grad|screen] [--prune-screen-radius PX] [--opacity-reset-interval K]"""
+        [--criterion xyz_grad|screen] [--prune-screen-radius PX] [--opacity-reset-interval K]
+        [--absgrad [--abs-threshold T]]"""
 import argparse
 import json
 import math
@@ -61,7 +62,8 @@ def build_scene(pkg, views=100, size=800, gt_gaussians=200_000, device=None):
 
 
 def make_trainer(pkg, ds, iters=7000, **density):
-    """density: TrainingConfig's densify_criterion / prune_screen_radius / opacity_reset_interval."""
+    """density: TrainingConfig's densify_criterion / prune_screen_radius / opacity_reset_interval /
+    densify_absgrad / densify_abs_grad_threshold."""
     cfg = pkg.TrainingConfig(iterations=iters, num_random_points=100_000, log_interval=500,
                              densify_until_iter=min(15000, iters // 2), output_path=os.path.join(ds.root, "out"),
                              **density)
@@ -79,6 +81,8 @@ def main():
     ap.add_argument("--criterion", default="xyz_grad", help="TrainingConfig.densify_criterion")
     ap.add_argument("--prune-screen-radius", type=float, default=0.0)
     ap.add_argument("--opacity-reset-interval", type=int, default=0)
+    ap.add_argument("--absgrad", action="store_true", help="TrainingConfig.densify_absgrad (with --criterion screen)")
+    ap.add_argument("--abs-threshold", type=float, default=0.0008, help="TrainingConfig.densify_abs_grad_threshold")
     ap.add_argument("--profile-iters", type=int, default=0,
                     help="host profile (cProfile) of this many iterations after 100 warm ones, then exit")
     a = ap.parse_args()
@@ -87,7 +91,8 @@ def main():
     ds = build_scene(pkg, a.views, a.size, a.gt_gaussians)
     n = a.gt_gaussians
     tr = make_trainer(pkg, ds, a.iters, densify_criterion=a.criterion, prune_screen_radius=a.prune_screen_radius,
-                      opacity_reset_interval=a.opacity_reset_interval)
+                      opacity_reset_interval=a.opacity_reset_interval, densify_absgrad=a.absgrad,
+                      densify_abs_grad_threshold=a.abs_threshold)
     if a.profile_iters:
         import cProfile
         import pstats
@@ -112,7 +117,7 @@ def main():
     v = tr.validate()
     print(json.dumps({"workload": f"C4 stand-in: synthetic Blender-format scene, {a.views} views {a.size}x{a.size}, "
                                   f"GT {n} Gaussians, random init 100k", "iterations": a.iters,
-                      "criterion": a.criterion, "it_per_s": round(a.iters / dt, 1), "train_s": round(dt, 2), "psnr_init": round(p0, 2),
+                      "criterion": a.criterion + (" + absgrad" if a.absgrad else ""), "it_per_s": round(a.iters / dt, 1), "train_s": round(dt, 2), "psnr_init": round(p0, 2),
                       "psnr_test": round(v["psnr"], 2), "gaussians": v["num_gaussians"],
                       "losses": [round(x, 4) for x in tr.train_losses]}), flush=True)
 
