@@ -56,11 +56,13 @@ extern "C" {
                                  later stages use: T, or 0 when the status is non-zero; [6..7] unused */
 /* Frame status bits (gs_bin_count, counters[4]): what a device-resident frame
  * (gs_render_fwd_args.device_counts) could not do on the device.  A frame
- * with a non-zero status is drawn with empty tile lists (memory-safe, not
- * the reference's image) and its caller renders it again on the host path. */
+ * with a non-zero status is drawn with empty tile lists (memory-safe); its
+ * image, alpha and depth are those of a frame that draws nothing (the
+ * background once, zeros: renderer.py:74-83, what the host path returns at
+ * M == 0), and its caller renders it again on the host path. */
 #define GS_FRAME_NEED_CAPACITY 1u /* T > the tile workspace's capacity */
 #define GS_FRAME_WINDOW_MISS 2u   /* a visible depth left the depth-key window (or an MSD bucket overflowed) */
-#define GS_FRAME_EMPTY 4u         /* M == 0: renderer.py:74-83's background image is the host's */
+#define GS_FRAME_EMPTY 4u         /* M == 0: nothing to draw (renderer.py:74-83's background image) */
 
 typedef enum gs_status {
   GS_OK = 0,
@@ -1131,7 +1133,8 @@ typedef struct gs_render_fwd_args {
    * count's status (GS_FRAME_*) and T stay on the device: the tile sort, the
    * ranges and the blend are launched for `capacity` entries (needs a tile
    * workspace) and read T themselves; a failed frame is drawn with empty
-   * lists and flagged in counters[4] (and *step_flags).  The call returns
+   * lists -- the background once, zero alpha and depth -- and flagged in
+   * counters[4] (and *step_flags).  The call returns
    * GS_OK with M, T unknown; the host reads (M, T, depth range, seq, status)
    * from the pinned counters whenever it likes.  For graph capture. */
   int32_t device_counts;

@@ -371,6 +371,23 @@ __global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32
   }
 }
 
+// A failed device-resident frame's pixels (gs_bin_count's status non-zero):
+// what a frame that draws nothing shows (renderer.py:74-83) -- the background
+// once, zero alpha and depth -- over the empty-list blend's bg + 1 * bg.  A
+// frame that succeeded leaves after one scalar load per wave.  Grid-stride.
+__global__ __launch_bounds__(kBlock) void k_failed_frame_pixels(const uint32_t *counters, float *image, float *alpha,
+                                                               float *depth, long long HW, float bg0, float bg1,
+                                                               float bg2) {
+  if (counters[4] == 0u) return;
+  for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < HW; p += (long long)gridDim.x * kBlock) {
+    image[p] = bg0;
+    image[HW + p] = bg1;
+    image[2 * HW + p] = bg2;
+    alpha[p] = 0.f;
+    depth[p] = 0.f;
+  }
+}
+
 // Every tile's [start, end) from the tile-sorted keys, empty tiles included
 // (no memset): position p in [0, T] is a boundary when key[p-1] != key[p]
 // (key[-1] = -1, key[T] = num_tiles); it closes the previous tile, opens the
@@ -502,3 +519,15 @@ gs_status gs_tile_ranges(const gs_range_args *a, gs_stream_t stream) {
 }
 
 }  // extern "C"
+
+gs_status gs_internal_failed_frame_pixels(const uint32_t *counters, const gs_camera *cam, float *image, float *alpha,
+                                          float *depth, gs_stream_t stream) {
+  if (!counters || !cam || !image || !alpha || !depth)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_internal_failed_frame_pixels");
+  const long long HW = (long long)cam->image_width * cam->image_height;
+  if (HW <= 0) return GS_OK;
+  const unsigned blocks = div_up(HW, kBlock);
+  k_failed_frame_pixels<<<blocks < 256u ? blocks : 256u, kBlock, 0, (hipStream_t)stream>>>(
+      counters, image, alpha, depth, HW, cam->bg[0], cam->bg[1], cam->bg[2]);
+  return gs_internal_check_launch("gs_internal_failed_frame_pixels");
+}

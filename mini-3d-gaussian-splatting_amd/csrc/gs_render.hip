@@ -342,7 +342,10 @@ gs_status gs_render_forward(gs_render_fwd_args *a, gs_stream_t stream) {
   fa.live_words = (int64_t)T0.live_words;
   fa.pair_counts = a->pair_counts;
   fa.num_pairs = T;
-  return gs_blend_forward(&fa, stream);
+  if ((st = gs_blend_forward(&fa, stream)) || !dev) return st;
+  // (a flagged frame's blend drew empty lists: bg + 1 * bg.  Its pixels become
+  // the frame's that draws nothing, as the host path returns it at M == 0)
+  return gs_internal_failed_frame_pixels(counters, &a->cam, a->image, a->alpha, a->depth, stream);
 }
 
 gs_status gs_render_backward(gs_render_bwd_args *a, gs_stream_t stream) {

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import golden_io as G
+from device_frame_util import index_statement
 from stubs import Cam, Gauss, grad_or_zero
 
 pytestmark = pytest.mark.gpu
@@ -1187,39 +1188,23 @@ def test_index_work_bit_exact(pkg, cuda, n, w, h, tile):
             torch.sigmoid(m._opacity).squeeze(1))
     torch.cuda.synchronize()
     M, T = fr.M, fr.T
-    vis = vis.cpu().numpy().astype(bool)
     z = fr.records.view(-1, 12)[:, 9].cpu().numpy()
     order = fr.order.cpu().numpy()[:M].astype(np.int64)
-    vidx = np.nonzero(vis)[0]
+    # the statement (device_frame_util.index_statement, shared with the device-resident frames' tests)
+    st = index_statement(means2d.cpu().numpy(), radii.cpu().numpy(), vis.cpu().numpy(), z, w, h, tile)
+    vidx = st.vidx
     assert M == len(vidx)
-    want_order = vidx[np.argsort(z[vidx], kind="stable")]
-    assert np.array_equal(order, want_order)
+    assert np.array_equal(order, st.order)
     # rectangles: renderer.py:278-293 from this frame's means and radii
-    mx, my = means2d.cpu().numpy().T.astype(np.float32)
-    ri = np.trunc(radii.cpu().numpy()).astype(np.int64)
-    icx, icy = np.trunc(mx).astype(np.int64), np.trunc(my).astype(np.int64)
-    x0, x1 = np.maximum(icx - ri, 0), np.minimum(icx + 1 + ri, w)
-    y0, y1 = np.maximum(icy - ri, 0), np.minimum(icy + 1 + ri, h)
     rects = fr.rects.view(-1, 2).cpu().numpy().astype(np.int64)
     gx0, gx1, gy0, gy1 = rects[:, 0] & 0xFFFF, rects[:, 0] >> 16, rects[:, 1] & 0xFFFF, rects[:, 1] >> 16
-    ne = (x0 < x1) & (y0 < y1)
-    v = vidx[ne[vidx]]
-    assert np.array_equal(gx0[v], x0[v] // tile) and np.array_equal(gx1[v], (x1[v] - 1) // tile)
-    assert np.array_equal(gy0[v], y0[v] // tile) and np.array_equal(gy1[v], (y1[v] - 1) // tile)
+    v = vidx[st.ne[vidx]]
+    assert np.array_equal(gx0[v], st.x0[v] // tile) and np.array_equal(gx1[v], (st.x1[v] - 1) // tile)
+    assert np.array_equal(gy0[v], st.y0[v] // tile) and np.array_equal(gy1[v], (st.y1[v] - 1) // tile)
     # tile lists: every (tile, Gaussian) of the depth-ordered rectangles, stable by tile
-    tiles_x, tiles_y = (w + tile - 1) // tile, (h + tile - 1) // tile
-    og = order[ne[order]]
-    nx = (x1[og] - 1) // tile - x0[og] // tile + 1
-    kk = nx * ((y1[og] - 1) // tile - y0[og] // tile + 1)
-    gs = np.repeat(og, kk)
-    local = np.arange(int(kk.sum())) - np.repeat(np.cumsum(kk) - kk, kk)  # rank in the rectangle, row-major
-    nxr = np.repeat(nx, kk)
-    keys = (np.repeat(y0[og] // tile, kk) + local // nxr) * tiles_x + np.repeat(x0[og] // tile, kk) + local % nxr
-    srt = np.argsort(keys, kind="stable")
-    assert T == len(keys)
-    assert np.array_equal(fr.sorted_gauss[:T].cpu().numpy().astype(np.int64), gs[srt])
-    counts = np.bincount(keys, minlength=tiles_x * tiles_y)
-    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    assert T == st.T
+    assert np.array_equal(fr.sorted_gauss[:T].cpu().numpy().astype(np.int64), st.gauss)
+    counts, starts = st.counts, st.starts
     rng_ = fr.ranges.cpu().numpy().astype(np.int64)
     nz = counts > 0
     assert np.array_equal(rng_[nz, 0], starts[nz]) and np.array_equal(rng_[nz, 1], (starts + counts)[nz])

@@ -13,8 +13,10 @@ pytestmark = pytest.mark.gpu
 N_G, W, H = 20_000, 320, 240
 
 
-def _setup(pkg, cuda, seed=0, shadow=False):
-    scene = pkg.synthetic.make_scene(N_G, W, H, seed=seed)
+def _setup(pkg, cuda, seed=0, shadow=False, n=N_G, W=W, H=H, edit=None):
+    scene = pkg.synthetic.make_scene(n, W, H, seed=seed)
+    if edit is not None:
+        edit(scene)  # (a test's own change to the seeded scene, before it goes to the device)
     model = pkg.synthetic.to_model(scene, pkg.GaussianModel, cuda)
     opt = pkg.optim.FusedAdam([{"params": [model._xyz], "lr": 1.6e-4}, {"params": [model._features_dc], "lr": 2.5e-3},
                                {"params": [model._opacity], "lr": 0.05}, {"params": [model._scaling], "lr": 5e-3},
@@ -208,3 +210,110 @@ def test_graph_replay_at_benchmark_size(pkg, cuda, size):
         assert a_[3] == b_[3]
         for x, y in zip(a_[:3], b_[:3]):
             assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize("capacity", [16384, 16385])
+def test_graph_replay_small_frame(pkg, cuda, capacity):
+    """A C1-sized step (5000 Gaussians, 256x256, T far below the capacity)
+    replayed with the tile workspace on either side of the one-workgroup
+    sort's edge, which the capacity decides, not T: 16384 sorts the tile keys
+    with gs_internal_small_sort, 16385 with the radix passes over n_dev.  No
+    redo; six steps equal six eager steps bit for bit, and the last replay's
+    image, alpha, depth and leaf gradients equal the eager frame's."""
+    n, w, h = 5000, 256, 256
+    ma, oa, cam, st, cot = _setup(pkg, cuda, seed=7, n=n, W=w, H=h)
+    out = _eager(pkg, ma, oa, cam, st, cot, 6)
+    assert 0 < pkg.rasterizer._T_SEEN[cuda] <= 16384
+    mb, ob, cam_b, st_b, cot_b = _setup(pkg, cuda, seed=7, n=n, W=w, H=h)
+    gs = pkg.GraphedStep(pkg.GaussianRenderer(), cam_b, mb, st_b, cot_b, ob)
+    gs.capacity = capacity
+    with torch.cuda.stream(gs.stream):
+        for _ in range(6):
+            gs.step()
+    gs.finish()
+    assert gs.redone == [] and gs.replays == 5 and gs._cap == capacity and not gs.disabled
+    _assert_same_state(ma, oa, mb, ob)
+    for k in ("image", "alpha", "depth"):
+        assert torch.equal(out[k].detach(), getattr(gs, k)), k
+    by_id = dict(zip(map(id, mb.grad_parameters()), ma.grad_parameters()))
+    for p, g in gs.leaf_grad:
+        assert torch.equal(by_id[id(p)].grad, g), "gradient of the last step"
+    gs.close()
+
+
+def test_graph_empty_frame_disables_the_graph(pkg, cuda):
+    """Every Gaussian behind the camera: the first replay flags
+    GS_FRAME_EMPTY; it is redone eagerly -- with the replay queued behind it,
+    unless the host saw the flag before it launched that one -- the
+    GraphedStep stays eager from then on (disabled), and five steps equal five
+    eager steps."""
+    def behind(scene):
+        scene.xyz[:, 2] *= -1.0
+    n = 3000
+    ma, oa, cam, st, cot = _setup(pkg, cuda, seed=9, n=n, edit=behind)
+    out = _eager(pkg, ma, oa, cam, st, cot, 5)
+    mb, ob, cam_b, st_b, cot_b = _setup(pkg, cuda, seed=9, n=n, edit=behind)
+    gs = pkg.GraphedStep(pkg.GaussianRenderer(), cam_b, mb, st_b, cot_b, ob)
+    with torch.cuda.stream(gs.stream):
+        gs.step()  # eager, then the capture
+        assert gs.graph is not None and not gs.disabled
+        gs.step()  # replay 1: flagged on the device
+        gs.step()  # replay 1 checked (the host reads its counters one step behind at the latest)
+        assert len(gs.redone) == 1 and gs.redone[0][0] == pkg._native.GS_FRAME_EMPTY, gs.redone
+        assert gs.redone[0][1] == gs.replays and gs.replays in (1, 2), (gs.redone, gs.replays)
+        assert gs.disabled is True
+        # the flagged replay's pixels are the empty frame's: the background once, zero alpha and depth
+        for k in ("image", "alpha", "depth"):
+            assert torch.equal(out[k].detach(), getattr(gs, k)), k
+        redone, replays = list(gs.redone), gs.replays
+        gs.step()
+        gs.step()
+        assert gs.replays == replays and gs.disabled is True, "a disabled GraphedStep steps eagerly"
+    gs.finish()
+    assert gs.redone == redone
+    _assert_same_state(ma, oa, mb, ob)
+    gs.close()
+
+
+def test_graph_msd_overflow_in_a_replay(pkg, cuda):
+    """The clumped-depth scene of test_depth_sort_msd_overflow_falls_back
+    (60 000 Gaussians, half of them within 1e-7 steps of z = 3) replayed with
+    a depth-key window and the MSD depth sort: a bucket over its capacity
+    poisons the frame's depth max on the device, the replay is flagged
+    GS_FRAME_WINDOW_MISS and redone, and five steps equal five eager steps."""
+    RZ = pkg.rasterizer
+    n = 60_000
+
+    def clump(scene):
+        g = torch.Generator().manual_seed(5)
+        z = torch.rand(n, generator=g) * 4 + 2
+        z[: n // 2] = 3.0 + torch.arange(n // 2, dtype=torch.float32) * 1e-7
+        scene.xyz[:, :2] *= (z / scene.xyz[:, 2])[:, None]
+        scene.xyz[:, 2] = z
+
+    def reset():
+        RZ._MSD_BACKOFF.clear()
+        RZ._WINDOW_STATE.pop(cuda, None)
+        RZ._DEPTH_HIST.pop(cuda, None)
+    reset()
+    try:
+        ma, oa, cam, st, cot = _setup(pkg, cuda, seed=3, n=n, edit=clump)
+        _eager(pkg, ma, oa, cam, st, cot, 5)
+        assert RZ._MSD_BACKOFF.get(cuda, 0) > 0, "the clump must overflow an MSD bucket on the eager path too"
+        reset()
+        mb, ob, cam_b, st_b, cot_b = _setup(pkg, cuda, seed=3, n=n, edit=clump)
+        gs = pkg.GraphedStep(pkg.GaussianRenderer(), cam_b, mb, st_b, cot_b, ob)
+        with torch.cuda.stream(gs.stream):
+            gs.step()  # eager with 32-bit keys (no depth range seen yet), then the capture
+            assert gs.window_used is not None and gs.fa.depth_sort_msd == 1, "the capture sorts windowed keys by MSD"
+            assert RZ._MSD_BACKOFF.get(cuda, 0) == 0
+            for _ in range(4):
+                gs.step()
+        gs.finish()
+        assert len(gs.redone) == 1 and gs.redone[0][0] == pkg._native.GS_FRAME_WINDOW_MISS, gs.redone
+        assert RZ._MSD_BACKOFF.get(cuda, 0) > 0, "the redo met the overflow on the host path (the poisoned depth max)"
+        assert gs.fa.depth_sort_msd == 0 and not gs.disabled
+        _assert_same_state(ma, oa, mb, ob)
+        gs.close()
+    finally:
+        reset()
