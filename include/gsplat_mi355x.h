@@ -1087,6 +1087,74 @@ typedef struct gs_mcmc_regularize_args {
 } gs_mcmc_regularize_args;
 gs_status gs_mcmc_regularize(const gs_mcmc_regularize_args *a, gs_stream_t stream);
 
+/* ---- 3D smoothing filter (Mip-Splatting, Yu et al. 2024, Sec. 4.1) ---------
+ * The other half of the anti-aliased mode (gs_screen_filter is the 2D half):
+ * every Gaussian is convolved in world space with an isotropic Gaussian of
+ * standard deviation f = sqrt(variance) / nu, nu the highest sampling rate
+ * (pixels per world unit, focal / depth) any training camera saw it at, so
+ * that no splat is thinner than what the training views could resolve.  The
+ * filter is a per-Gaussian map in front of the projection,
+ *   (scaling, opacity logit, f) -> (scaling', opacity'),
+ * whose outputs gs_gaussians takes as they are (scaling, opacity with
+ * opacity_is_logit = 0); the projection kernels do not know of it.  Stream
+ * ordered, one thread per Gaussian, no allocation, no atomics; every check
+ * below returns GS_ERR_INVALID_ARG before any HIP call; n == 0 is GS_OK with
+ * nothing launched. */
+#define GS_FILTER3D_CAMERA_FLOATS 18
+
+/* gs_filter3d_accumulate: the sampling-rate pass over num_cameras cameras in
+ * one launch (each position is read once).  A camera row is
+ *   {view[12] (row-major 3x4, world -> camera), fx, fy, cx, cy, W, H}.
+ * Per Gaussian and camera, in double from the fp32 inputs: (X, Y, Z) = R x + t;
+ * the camera sees the Gaussian iff Z > near and
+ *   -margin W <= fx X / Z + cx <= (1 + margin) W,
+ *   -margin H <= fy Y / Z + cy <= (1 + margin) H;
+ * its rate is max(fx, fy) / Z.  Then
+ *   max_rate[g] = fmaxf(max_rate[g], (float)(max over the seeing cameras)),
+ * and a Gaussian no camera sees keeps its value.  num_cameras == 0: GS_OK,
+ * nothing launched. */
+typedef struct gs_filter3d_rate_args {
+  int32_t n;
+  const float *xyz;      /* [n, xyz_stride] */
+  int64_t xyz_stride;    /* floats between rows, >= 3 */
+  const float *cameras;  /* device [num_cameras, GS_FILTER3D_CAMERA_FLOATS] */
+  int32_t num_cameras;
+  float near;            /* finite, > 0 (Mip-Splatting: 0.2) */
+  float margin;          /* finite, >= 0 (Mip-Splatting: 0.15) */
+  float *max_rate;       /* [n] in/out */
+} gs_filter3d_rate_args;
+gs_status gs_filter3d_accumulate(const gs_filter3d_rate_args *a, gs_stream_t stream);
+
+/* gs_filter3d_forward / gs_filter3d_backward: the map and its gradient.
+ *   s'_k = 1/2 log(exp(2 s_k) + f^2)
+ *   o'   = sigmoid(o) sqrt(prod_k exp(2 s_k) / (exp(2 s_k) + f^2))
+ * (o' a probability), computed without overflow as, L = log f,
+ * d_k = 2 (s_k - L) -- both formed in double from the fp32 inputs and rounded
+ * to fp32 once -- and r_k = sigmoid(d_k), in fp32:
+ *   s'_k = max(s_k, L) + 1/2 log1pf(expf(-|d_k|)),  coef = sqrtf(r_0 r_1 r_2),
+ *   o' = sigmoid(o) coef.
+ * A row with f == 0 copies s bit for bit and writes sigmoid(o).  The backward
+ * stores (does not add)
+ *   d_scaling_k = g_scaling_out_k r_k + g_opacity_out o' (1 - r_k)
+ *   d_opacity   = g_opacity_out coef sigmoid(o) (1 - sigmoid(o))
+ * with 1 - r_k formed as sigmoid(-d_k); f carries no gradient; f == 0:
+ * d_scaling = g_scaling_out bit for bit.  All rows are dense.  The forward
+ * reads the first five pointers, the backward all but the two outputs. */
+typedef struct gs_filter3d_args {
+  int32_t n;
+  const float *scaling;   /* [n,3] log */
+  const float *opacity;   /* [n] logit */
+  const float *filter;    /* [n] f >= 0, world units */
+  float *scaling_out;     /* [n,3] log (forward) */
+  float *opacity_out;     /* [n] probability (forward) */
+  const float *g_scaling_out; /* [n,3] (backward) */
+  const float *g_opacity_out; /* [n] (backward) */
+  float *d_scaling;       /* [n,3] (backward) */
+  float *d_opacity;       /* [n] (backward) */
+} gs_filter3d_args;
+gs_status gs_filter3d_forward(const gs_filter3d_args *a, gs_stream_t stream);
+gs_status gs_filter3d_backward(const gs_filter3d_args *a, gs_stream_t stream);
+
 /* ---- Frame entry points: the stages above in one call per direction -------
  * gs_render_forward runs what GaussianRenderer.render does (renderer.py:31-114)
  * -- projection + culling, depth sort, binning, tile sort, ranges, blend --

@@ -335,6 +335,20 @@ class GsMcmcRegularizeArgs(C.Structure):
                 ("lambda_opacity", C.c_float), ("lambda_scale", C.c_float)]
 
 
+GS_FILTER3D_CAMERA_FLOATS = 18  # {view[12], fx, fy, cx, cy, W, H} per camera row of the rate pass
+
+
+class GsFilter3dRateArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("xyz", _vp), ("xyz_stride", C.c_int64), ("cameras", _vp),
+                ("num_cameras", C.c_int32), ("near", C.c_float), ("margin", C.c_float), ("max_rate", _vp)]
+
+
+class GsFilter3dArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("scaling", _vp), ("opacity", _vp), ("filter", _vp), ("scaling_out", _vp),
+                ("opacity_out", _vp), ("g_scaling_out", _vp), ("g_opacity_out", _vp), ("d_scaling", _vp),
+                ("d_opacity", _vp)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -349,6 +363,7 @@ EXPORTS = (
     "gs_blend_distortion_forward", "gs_blend_distortion_backward",
     "gs_mcmc_sample", "gs_mcmc_relocate_workspace_bytes", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize",
     "gs_blend_backward_abs", "gs_gather_abs_partials", "gs_density_accumulate_abs",
+    "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
 )
 
 _lib = None
@@ -426,6 +441,9 @@ def _declare(lib):
     lib.gs_blend_backward_abs.argtypes = [P(GsBlendBwdArgs), _vp, _vp]
     lib.gs_gather_abs_partials.argtypes = [P(GsAbsGatherArgs), _vp]
     lib.gs_density_accumulate_abs.argtypes = [P(GsDensityAbsArgs), _vp]
+    lib.gs_filter3d_accumulate.argtypes = [P(GsFilter3dRateArgs), _vp]
+    lib.gs_filter3d_forward.argtypes = [P(GsFilter3dArgs), _vp]
+    lib.gs_filter3d_backward.argtypes = [P(GsFilter3dArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
@@ -433,7 +451,7 @@ def _declare(lib):
               "gs_blend_contributions", "gs_contrib_accumulate", "gs_blend_distortion_forward",
               "gs_blend_distortion_backward", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
               "gs_mcmc_regularize", "gs_blend_backward_abs", "gs_gather_abs_partials",
-              "gs_density_accumulate_abs"):
+              "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -75,6 +75,13 @@ class TrainingConfig:
     # opacities are scaled so that a filtered splat keeps its energy
     screen_filter: float = 0.0
     filter_compensate: bool = True
+    # Mip-Splatting's 3D smoothing filter in every render, training and evaluation (filter3d.Filter3D;
+    # with screen_filter = 0.1 the pair is Mip-Splatting's anti-aliased mode): its variance in px^2 at
+    # each Gaussian's highest training sampling rate, and how often (iterations) the rates are recomputed
+    # from all training cameras -- besides every time the rows change (densification, relocation, pruning)
+    filter_3d: bool = False
+    filter_3d_variance: float = 0.2
+    filter_3d_interval: int = 100
     # contribution pruning (GaussianTrainer.compact): at these iterations, after the optimizer step,
     # every training camera is rendered and the Gaussians whose largest blend weight over all of them
     # is not above the threshold are dropped (0.01: RadSplat's default); () = never
@@ -119,6 +126,12 @@ class TrainingConfig:
         s = float(self.screen_filter)
         if not (s >= 0.0 and s != float("inf")):
             raise ValueError(f"screen_filter must be a finite variance >= 0 (px^2), got {self.screen_filter!r}")
+        v = float(self.filter_3d_variance)
+        if not (v >= 0.0 and v != float("inf")):
+            raise ValueError(f"filter_3d_variance must be a finite variance >= 0 (px^2), got {self.filter_3d_variance!r}")
+        it = self.filter_3d_interval
+        if isinstance(it, bool) or not isinstance(it, int) or it < 1:
+            raise ValueError(f"filter_3d_interval must be an integer >= 1, got {it!r}")
         if not float(self.contribution_prune_threshold) >= 0.0:
             raise ValueError(f"contribution_prune_threshold must be >= 0, got {self.contribution_prune_threshold!r}")
         its = self.contribution_prune_iterations

@@ -33,6 +33,10 @@ Differences a caller can observe (all documented in DESIGN.md):
   * `settings.screen_filter` (not in the reference; default 0 = off) low-pass
     filters every splat in screen space, cov2d + s I, and with
     `settings.filter_compensate` keeps its energy (anti-aliasing).
+  * `render(..., filter_3d=Filter3D)` (not in the reference) convolves every
+    Gaussian with Mip-Splatting's 3D smoothing filter before the projection
+    (filter3d.py); with `settings.screen_filter` the pair is its anti-aliased
+    mode.
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
     switches on view-dependent SH colour; at 0 -- the default for the
     reference's own model and stubs -- colours are the reference's
@@ -47,6 +51,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _native as N
+from .filter3d import Filter3D, apply_filter_3d, check_filter_3d_variance
 from .rasterizer import (CameraParams, ContributionStats, DensityStats, check_distortion_near_far,
                          check_screen_filter, rasterize)
 
@@ -134,6 +139,24 @@ def camera_params(camera, settings: RenderSettings, radius_min=0.01, radius_max=
                         float(getattr(settings, "screen_filter", 0.0)), bool(getattr(settings, "filter_compensate", True)))
 
 
+def _check_filter_3d(filter_3d, gaussians, fused) -> None:
+    """ValueError for a filter_3d this render cannot apply, before any launch."""
+    if not isinstance(filter_3d, Filter3D):
+        raise ValueError(f"filter_3d must be a Filter3D, got {type(filter_3d).__name__}")
+    if not fused:
+        raise ValueError("filter_3d needs this package's GaussianModel (scaling and rotation): a model rendered "
+                         "through get_covariance cannot take the 3D filter")
+    check_filter_3d_variance(filter_3d.variance)
+    s, v = gaussians._scaling, filter_3d.values
+    if v.dim() != 1 or v.shape[0] != s.shape[0] or filter_3d.n != s.shape[0]:
+        raise ValueError(f"filter_3d holds {tuple(v.shape)} values for a model of {s.shape[0]} Gaussians")
+    if v.device != s.device:
+        raise ValueError(f"filter_3d is on {v.device}, the model on {s.device}")
+    if v.dtype != torch.float32 or s.dtype != torch.float32 or gaussians._opacity.dtype != torch.float32:
+        raise ValueError(f"filter_3d needs fp32 values, scaling and opacity, got {v.dtype}, {s.dtype}, "
+                         f"{gaussians._opacity.dtype}")
+
+
 class GaussianRenderer:
     """renderer.py:22-114"""
 
@@ -156,8 +179,19 @@ class GaussianRenderer:
                density_stats: Optional[DensityStats] = None,
                contribution_stats: Optional[ContributionStats] = None,
                dominant: bool = False, depth_distortion: bool = False,
-               distortion_near_far=None) -> Dict[str, torch.Tensor]:
-        """depth_distortion: the result also holds
+               distortion_near_far=None, filter_3d: Optional[Filter3D] = None) -> Dict[str, torch.Tensor]:
+        """filter_3d: optional Filter3D of the model's size on its device
+        (Mip-Splatting's 3D smoothing filter, filter3d.py).  The model's raw
+        _scaling and _opacity then pass through apply_filter_3d and the
+        projection reads the results: scaling' and the probability opacity'.
+        Gradients reach the leaves through autograd; a data-parallel bucket is
+        not written by the kernels then (the projection's d_scaling is
+        scaling''s, not the leaf's) and takes the .grad tensors at its
+        all-reduce.  Only this package's GaussianModel: a duck-typed model (the
+        get_covariance path), a size, device or dtype mismatch, or a negative
+        or non-finite variance is a ValueError before anything is launched.
+        None is the render without the argument, launch for launch.
+        depth_distortion: the result also holds
           "distortion"      fp32 [H, W]: sum_i sum_j c_i c_j |m_i - m_j| over
                             the pixel's contributors, with the colour pass's
                             own weights c -- how spread out along the ray they
@@ -230,6 +264,8 @@ class GaussianRenderer:
         pose = {"view": wv} if wv.requires_grad else {}
         xyz = gaussians.get_xyz
         fused = getattr(gaussians, "_gs_fused_covariance", False)
+        if filter_3d is not None:
+            _check_filter_3d(filter_3d, gaussians, fused)
         if fused:
             # this package's GaussianModel: covariance from the raw scaling /
             # rotation and get_opacity's sigmoid are computed in the kernels;
@@ -246,6 +282,10 @@ class GaussianRenderer:
             else:
                 logits = gaussians._features_dc.squeeze(1)
         opacity = gaussians._opacity if fused else gaussians.get_opacity.squeeze(1)
+        opacity_is_logit = fused
+        if filter_3d is not None:
+            scaling, opacity = apply_filter_3d(scaling, opacity, filter_3d.values)
+            opacity_is_logit = False
         sh_degree = settings.sh_degree
         if sh_degree is None:
             sh_degree = int(getattr(gaussians, "active_sh_degree", 0))
@@ -253,7 +293,9 @@ class GaussianRenderer:
         if sh_degree > 0:
             sh_rest = gaussians._features_rest if fused else feats[:, 1:, :]
         grad_dest = None
-        sink = getattr(gaussians, "_gs_grad_sink", None) if fused else None
+        # (with a 3D filter the projection's scaling / opacity gradients are those of
+        # the map's outputs: they must not land in the bucket as the leaves')
+        sink = getattr(gaussians, "_gs_grad_sink", None) if fused and filter_3d is None else None
         if sink is not None:
             # data-parallel bucket (distributed.GradAllReduce.attach): the
             # gradient kernels write straight into it when it can take them
@@ -289,7 +331,7 @@ class GaussianRenderer:
         if depth_distortion:
             extra["depth_distortion"], extra["distortion_near_far"] = True, distortion_near_far
         image, alpha, depth, means2d, conics, radii, vis, *feature_image = rasterize(
-            cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=fused,
+            cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=opacity_is_logit,
             sh_rest=sh_rest, sh_degree=sh_degree, grad_dest=grad_dest, **extra)
         # the reference's output dtypes (renderer.py:74-83, :273-275, :359-367):
         # the projection outputs in the Gaussians' dtype, image in the

@@ -12,7 +12,10 @@ absolute gradient among them, which the split test then reads; then also
 prune_screen_radius and, every opacity_reset_interval iterations, the 3DGS
 opacity reset), or with densify_criterion = "mcmc" the 3DGS-MCMC family
 (_mcmc_update: regularisers, relocation and capped growth in place of split /
-clone / prune, position noise every iteration).  With lambda_distortion > 0 the
+clone / prune, position noise every iteration).  With filter_3d every render
+-- training, validation, contribution pruning -- applies Mip-Splatting's 3D
+smoothing filter, recomputed from all training cameras every
+filter_3d_interval iterations and whenever the rows change.  With lambda_distortion > 0 the
 loss gains, from distortion_from_iter on, lambda_distortion times the mean
 depth distortion of the view (render(depth_distortion=True)).  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.
@@ -33,6 +36,7 @@ import torch
 
 from .config import TrainingConfig
 from .dataset import CameraDataset, load_dataset
+from .filter3d import Filter3D
 from .gaussian_model import GaussianModel
 from .loss import photometric_loss
 from .optim import GaussianOptimizer
@@ -56,6 +60,7 @@ class GaussianTrainer:
         self._perm: Optional[np.ndarray] = None
         self.last_densify: Optional[dict] = None  # the counts of the latest densification
         self.last_compact: Optional[dict] = None  # the counts of the latest contribution pruning
+        self.filter_3d: Optional[Filter3D] = None  # config.filter_3d: the 3D smoothing filter of every render
 
     # -- setup (trainer.py:32-44) ------------------------------------------
     def _device(self) -> torch.device:
@@ -93,6 +98,21 @@ class GaussianTrainer:
         self.gaussians = g
         self.optimizer = GaussianOptimizer(g, c)
         self.optimizer.setup_optimizer()
+        self._update_filter_3d()
+
+    def _update_filter_3d(self) -> None:
+        """config.filter_3d: the filter of the current rows from all training
+        cameras (every rank the full list: the replicas' filters are the same
+        bits)."""
+        if not self.config.filter_3d:
+            return
+        xyz = self.gaussians._xyz.detach()
+        if self.filter_3d is None or self.filter_3d.n != xyz.shape[0]:
+            self.filter_3d = Filter3D(xyz.shape[0], xyz.device, self.config.filter_3d_variance)
+        self.filter_3d.update(self.dataset.get_train_cameras(), xyz)
+
+    def _render_extra(self) -> dict:
+        return {} if self.filter_3d is None else {"filter_3d": self.filter_3d}
 
     def get_scene_extent(self) -> float:
         """trainer.py:87-89: camera-centre radius (get_scene_info)."""
@@ -117,6 +137,8 @@ class GaussianTrainer:
                 and self.iteration > 0 and self.iteration % c.sh_increase_interval == 0):
             g.max_sh_degree = max(g.max_sh_degree, c.sh_degree)
             g.oneup_sh_degree()
+        if c.filter_3d and self.iteration % c.filter_3d_interval == 0:
+            self._update_filter_3d()
         opt.zero_grad()
         if self._dist is not None:
             # the bucket is attached before the render, so that its backward
@@ -127,7 +149,7 @@ class GaussianTrainer:
                 self._reducer = GradAllReduce(params, self._dist).attach(g)
                 self._reducer_n = g.get_num_points()
             self._reducer.params = params
-        extra = {}
+        extra = self._render_extra()
         if c.densify_criterion == "screen":
             extra["density_stats"] = g.density_stats
         # the distortion term: the eager stage path (no replayed step renders it)
@@ -156,6 +178,7 @@ class GaussianTrainer:
         if info is not None:
             self._reducer = None
             self.last_densify = info
+            self._update_filter_3d()
         if (c.opacity_reset_interval > 0 and self.iteration % c.opacity_reset_interval == 0
                 and self.iteration <= c.densify_until_iter):
             opt.cap_opacity()
@@ -181,6 +204,7 @@ class GaussianTrainer:
             self.last_densify = info
             if info["added"]:
                 self._reducer = None
+            self._update_filter_3d()
         opt.mcmc_noise(self.iteration)
         if c.contribution_prune_iterations and self.iteration in c.contribution_prune_iterations:
             self.last_compact = self.compact()
@@ -206,12 +230,13 @@ class GaussianTrainer:
         stats = g.contribution_stats
         stats.reset()
         for cam in cams:
-            self.renderer.render(cam, g, self._settings(cam), contribution_stats=stats)
+            self.renderer.render(cam, g, self._settings(cam), contribution_stats=stats, **self._render_extra())
         if self._dist is not None:
             stats.all_reduce(self._dist)
         info = self.optimizer.prune_by_contribution(stats, threshold)
         self._reducer = None  # (the bucket was sized for the old N)
         g.contribution_stats.reset()
+        self._update_filter_3d()
         return info
 
     def close(self) -> None:
@@ -243,7 +268,7 @@ class GaussianTrainer:
         cams = self.dataset.get_test_cameras() or self.dataset.get_train_cameras()
         psnr, loss = [], []
         for cam in cams:
-            img = self.renderer.render(cam, self.gaussians, self._settings(cam))["image"]
+            img = self.renderer.render(cam, self.gaussians, self._settings(cam), **self._render_extra())["image"]
             mse = torch.mean((img - cam._image) ** 2)
             psnr.append(-10.0 * torch.log10(mse.clamp_min(1e-12)))
             loss.append(photometric_loss(img, cam._image, self.config.lambda_dssim)[0])
@@ -268,6 +293,9 @@ class GaussianTrainer:
                 tensors[f"adam.{name}.m"] = st["exp_avg"].contiguous()
                 tensors[f"adam.{name}.v"] = st["exp_avg_sq"].contiguous()
                 tensors[f"adam.{name}.step"] = torch.tensor([st["step"]], dtype=torch.int64)
+        if self.filter_3d is not None:
+            for name, v in self.filter_3d.state().items():
+                tensors[f"filter_3d.{name}"] = v.contiguous()
         path = self._ckpt_path(iteration)
         save_file({k: v.cpu() for k, v in tensors.items()}, path,
                   metadata={"iteration": str(iteration), "active_sh_degree": str(self.gaussians.active_sh_degree)})
@@ -296,6 +324,14 @@ class GaussianTrainer:
         self._reducer = None
         if self._perm is None:
             self._setup_run()
+        if self.config.filter_3d:
+            n = self.gaussians.get_num_points()
+            if "filter_3d.values" in t:
+                self.filter_3d = Filter3D(n, dev, self.config.filter_3d_variance)
+                self.filter_3d.load_state({k: t[f"filter_3d.{k}"] for k in ("max_rate", "values")})
+            else:  # (a checkpoint of a run without the filter)
+                self.filter_3d = None
+                self._update_filter_3d()
 
 
 __all__ = ["GaussianTrainer", "TrainingConfig"]
