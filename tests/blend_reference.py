@@ -402,13 +402,27 @@ def emulate_tile(fr, t, g_image, g_alpha=None, g_depth=None, recenter=True):
             g = np.where(ai_all[i] == u_all[i], dal * w_all[i], zero)
             dop[i] = np.where(c > 0, g, zero)
             cw[i] = np.where(w_all[i] == e_all[i], c, -c)
-        # phase B: column and row moments per (entry, cell)
+        out["partials"] = emulate_phase_b(fr, t, rec, xs, ys, cq, dop, cw,
+                                          np.concatenate([gR, gD[:, None]], 1), recenter)
+    return out
+
+
+def emulate_phase_b(fr, t, rec, xs, ys, cq, dop, cw, gRD, recenter=True):
+    """Phase B of the backward in numpy fp32: the column and row moments per
+    (entry, cell) from phase A's dop and +-c [n, P] and the pixels' payload
+    cotangents gRD [P, 4].  recenter: True, the rows of an entry with
+    sigma_y < 2 px about the row nearest its mean; False, every row moment
+    about row 0; "always", every entry recentred (the replays of
+    gs_features.hip).  Returns the partials [n, cells, 10]."""
+    n = len(rec)
+    one, zero = F32(1), F32(0)
+    o = rec[:, 5]
+    with np.errstate(all="ignore"):
         Q = fr.cells
         part = np.zeros((n, Q, 10), F32)
         q00, q11, qo = rec[:, 2], rec[:, 3], rec[:, 4]
         hop = F32(-0.5) * o
-        sm = small_y(rec)
-        gRD = np.concatenate([gR, gD[:, None]], 1)
+        sm = np.ones(n, bool) if recenter == "always" else small_y(rec) & bool(recenter)
         for q in range(Q):
             m = cq == q
             if not m.any():
@@ -419,7 +433,7 @@ def emulate_tile(fr, t, g_image, g_alpha=None, g_depth=None, recenter=True):
             pgq = np.zeros((8, 8, 4), F32)
             rr, cc = ys[m] - y0c, xs[m] - x0c
             dq[:, rr, cc], cq_[:, rr, cc], pgq[rr, cc] = dop[:, m], cw[:, m], gRD[m]
-            rc = np.where(sm & recenter, np.clip(np.rint(rec[:, 1] - F32(y0c)), 0, 7), 0).astype(F32)  # [n]
+            rc = np.where(sm, np.clip(np.rint(rec[:, 1] - F32(y0c)), 0, 7), 0).astype(F32)  # [n]
             S0 = np.zeros((n, 8), F32)
             Soy, Soyy, g5 = S0.copy(), S0.copy(), S0.copy()
             g69 = np.zeros((n, 8, 4), F32)
@@ -442,8 +456,7 @@ def emulate_tile(fr, t, g_image, g_alpha=None, g_depth=None, recenter=True):
             part[:, q, 1] = -(qo * Sx + F32(2) * q11 * Sy)
             part[:, q, 2], part[:, q, 3], part[:, q, 4], part[:, q, 5] = g2, g3, g4, g5
             part[:, q, 6:10] = g69.sum(1, dtype=F32)
-        out["partials"] = part
-    return out
+    return part
 
 
 def ratio(err, M, n_p):
@@ -494,9 +507,11 @@ def frame_from_screen(means2d, conics, radii, vis, opacity, colour, z, W, H, L, 
 
 
 def cpu_frame(sc):
-    """A scene (make_scene) as a host frame: projected in fp64, rounded to fp32."""
+    """A scene (make_scene) as a host frame: projected in fp64, rounded to fp32.
+    sc["fx"], where present, is its focal length in place of FX."""
     W, H = sc["W"], sc["H"]
-    cam = PR.Camera(W, H, FX, FX, W * 0.5, H * 0.5, (1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0), tile_size=sc["L"])
+    fx = float(sc.get("fx", FX))
+    cam = PR.Camera(W, H, fx, fx, W * 0.5, H * 0.5, (1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0), tile_size=sc["L"])
     t64 = lambda a: torch.from_numpy(np.asarray(a, np.float64))
     p = PR.project(cam, t64(sc["xyz"]), t64(sc["color_logits"]), t64(sc["opacity"]), cov3d=t64(sc["cov3d"]))
     f32 = lambda k: p[k].numpy().astype(F32)
@@ -520,6 +535,16 @@ def make_scene(W, H, L, mx, my, z, sx, sy, theta, opacity, colour, bg=(0.0, 0.0,
     return dict(W=W, H=H, L=L, xyz=np.stack([X, Y, z], 1).astype(F32), cov3d=cov.astype(F32),
                 opacity=np.asarray(opacity, F32), color_logits=np.log(colour / (1 - colour)).astype(F32),
                 bg=np.asarray(bg, F32))
+
+
+def fd_scene():
+    """6 Gaussians on 8x8 pixels, one tile, one cell, away from every
+    decision: the scene of the finite-difference tests."""
+    rng = np.random.default_rng(5)
+    n = 6
+    return make_scene(8, 8, 8, rng.uniform(1, 7, n), rng.uniform(1, 7, n), np.linspace(2, 4, n), rng.uniform(2.5, 4, n),
+                      rng.uniform(2.5, 4, n), rng.uniform(-0.5, 0.5, n), rng.uniform(0.1, 0.4, n),
+                      rng.uniform(0.2, 0.8, (n, 3)), bg=(0.05, 0.1, 0.02))
 
 
 def _random_scene(seed, n, W, H, L, sigma, opacity, bg=(0.0, 0.0, 0.0), thin=0.0):

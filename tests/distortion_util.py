@@ -1,8 +1,11 @@
 """Helpers of tests/test_distortion_cpu.py and tests/test_distortion_gpu.py:
 the fp64 reference of the depth distortion and the fp32-sequential median
 rule, both built from the weight image Wt[g, p] = c_g(p) that a render with
-features = eye(N) returns (pinned to the oracle by the feature tests); the
-same formula in torch fp64 for the gradient reference; the built scene of
+features = eye(N) returns (pinned to the oracle at 1e-4 by the feature
+tests and, per float against an fp64 statement that owes nothing to the
+replay kernels, by tests/test_replay_stage.py, which also checks k_dist_fwd
+and k_dist_bwd themselves per pixel and per gradient partial); the same
+formula in torch fp64 for the gradient reference; the built scene of
 the cancellation test; and the child process of the cell-batch / no-bitmap
 tests (the budgets are read at import)."""
 import os

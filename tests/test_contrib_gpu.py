@@ -2,7 +2,10 @@
 contribution pruning on the GPU.  The reference for the weights is the feature
 pass with features = eye(N): its image, already checked against the oracle
 (tests/test_features_gpu.py), is Wt[g, p] = fma(c_g(p), 1, 0) plus exact
-zeros = c_g(p)."""
+zeros = c_g(p).  That image comes from k_feat_fwd, a sibling of the kernels
+under test; what pins it, and k_contrib and k_contrib_gather themselves, to
+something independent is tests/test_replay_stage.py: every float against an
+fp64 statement, not only the oracle at 1e-4."""
 import dataclasses
 import os
 import subprocess
