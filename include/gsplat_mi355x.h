@@ -819,6 +819,34 @@ typedef struct gs_adam_args {
 } gs_adam_args;
 gs_status gs_adam_step(const gs_adam_args *a, gs_stream_t stream);
 
+/* Visibility-gated Adam (gsplat's visible_adam / SelectiveAdam, the sparse
+ * Adam of Taming 3DGS): the update of gs_adam_step -- the same fp32
+ * operations, lr, bias corrections and one_minus_beta* rounding -- on the
+ * rows whose row_mask byte is non-zero only.  Every tensor with a grad is
+ * [rows, cols[i]] row-major.  A row with row_mask[r] == 0 keeps the bits of
+ * param, exp_avg and exp_avg_sq, and its gradient is never used (NaN / Inf
+ * included; it is not even loaded where no element of its float4 is visible).
+ * A workgroup owns GS_ADAM_ROW_BLOCK consecutive rows of one tensor: it reads
+ * their mask bytes first and returns before any load of p, g, m or v when
+ * none is set.  No atomics: bitwise reproducible, and bit-identical to
+ * gs_adam_step on the visible rows.
+ * param_out, skip_flag, hyper and hyper_row are not supported here
+ * (GS_ERR_UNSUPPORTED when non-NULL), nor is cols[i] above
+ * GS_ADAM_ROWS_MAX_COLS (the row of an element is found with a 32-bit
+ * multiply-high, exact up to there).  GS_ERR_INVALID_ARG, before any HIP
+ * call: NULL row_mask, rows < 0, cols[i] < 1, numel != rows * cols[i], a NULL
+ * buffer behind a non-NULL grad.  rows == 0 or no tensor with a grad: GS_OK,
+ * nothing launched. */
+#define GS_ADAM_ROW_BLOCK 256          /* rows one workgroup owns; a multiple of 4 */
+#define GS_ADAM_ROWS_MAX_COLS 2047
+typedef struct gs_adam_rows_args {
+  gs_adam_args adam;                   /* as gs_adam_step: betas, eps, one_minus_beta*, t[0..num_tensors) */
+  int64_t rows;                        /* dim 0 shared by every tensor with a grad */
+  int32_t cols[GS_ADAM_MAX_TENSORS];   /* t[i].numel == rows * cols[i], cols[i] >= 1 */
+  const uint8_t *row_mask;             /* [rows]; non-zero: update the row */
+} gs_adam_rows_args;
+gs_status gs_adam_step_rows(const gs_adam_rows_args *a, gs_stream_t stream);
+
 /* Optimizer in the backward (opt-in; one rank, no gradient hooks): the
  * projection backward of the training configuration (raw scaling / rotation,
  * opacity logit, DC colour, blend sums in grad_sums or pair_grads, no

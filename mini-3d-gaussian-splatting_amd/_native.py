@@ -249,6 +249,16 @@ class GsAdamArgs(C.Structure):
     ]
 
 
+GS_ADAM_ROW_BLOCK = 256  # rows one workgroup of gs_adam_step_rows owns
+GS_ADAM_ROWS_MAX_COLS = 2047
+
+
+class GsAdamRowsArgs(C.Structure):
+    _fields_ = [
+        ("adam", GsAdamArgs), ("rows", C.c_int64), ("cols", C.c_int32 * GS_ADAM_MAX_TENSORS), ("row_mask", _vp),
+    ]
+
+
 GS_LOSS_MAX_WINDOW = 11
 
 
@@ -364,6 +374,7 @@ EXPORTS = (
     "gs_mcmc_sample", "gs_mcmc_relocate_workspace_bytes", "gs_mcmc_relocate", "gs_mcmc_noise", "gs_mcmc_regularize",
     "gs_blend_backward_abs", "gs_gather_abs_partials", "gs_density_accumulate_abs",
     "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
+    "gs_adam_step_rows",
 )
 
 _lib = None
@@ -415,6 +426,7 @@ def _declare(lib):
     lib.gs_tile_offsets.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, P(C.c_size_t)]
     lib.gs_tile_offsets.restype = None
     lib.gs_adam_step.argtypes = [P(GsAdamArgs), _vp]
+    lib.gs_adam_step_rows.argtypes = [P(GsAdamRowsArgs), _vp]
     lib.gs_project_backward_adam.argtypes = [P(GsProjectBwdArgs), P(GsAdamArgs), _vp]
     lib.gs_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.gs_loss_workspace_bytes.restype = C.c_size_t
@@ -451,7 +463,8 @@ def _declare(lib):
               "gs_blend_contributions", "gs_contrib_accumulate", "gs_blend_distortion_forward",
               "gs_blend_distortion_backward", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
               "gs_mcmc_regularize", "gs_blend_backward_abs", "gs_gather_abs_partials",
-              "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward"):
+              "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
+              "gs_adam_step_rows"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -105,6 +105,11 @@ class TrainingConfig:
     lambda_distortion: float = 0.0
     distortion_from_iter: int = 0
     distortion_near_far: Optional[tuple] = None
+    # visibility-gated Adam (gsplat's visible_adam, the sparse Adam of Taming 3DGS): a step updates only the
+    # Gaussians its view saw (the render's visibility_filter; data parallel: the union over the ranks' views);
+    # every other row keeps its parameters and both Adam moments bit for bit instead of drifting along a
+    # stale first moment.  Step counts stay per tensor.  Not for the replayed step (GraphedStep)
+    visible_adam: bool = False
 
     def __post_init__(self):
         # (a YAML file holds the iterations as a list)

@@ -328,27 +328,30 @@ class GradAllReduce:
             flat.div_(world)
         self._copy_out(views, in_place)
 
-    def reduce_and_step(self, optimizer) -> None:
+    def reduce_and_step(self, optimizer, visible=None) -> None:
         """all_reduce_mean() then optimizer.step(), pipelined when the
         backward handed its rows over in ranges (rows_ready) and every
         gradient is the bucket itself: range k's Adam update is queued behind
         range k's all-reduce only (FusedAdam.step_ranges), so it overlaps the
         reductions of the later ranges.  Bit-identical to the unpipelined
-        sequence (the same reduced values, an elementwise update)."""
+        sequence (the same reduced values, an elementwise update).  visible:
+        the step's row mask, the same on every rank (FusedAdam.step; the
+        trainer hands in the union of the ranks' visibility), passed on to
+        step / step_ranges; None: the dense update."""
         t0 = time.perf_counter()
         try:
-            self._reduce_and_step(optimizer)
+            self._reduce_and_step(optimizer, {} if visible is None else {"visible": visible})
         finally:
             self.host_s["reduce_and_step"] += time.perf_counter() - t0
 
-    def _reduce_and_step(self, optimizer) -> None:
+    def _reduce_and_step(self, optimizer, kw) -> None:
         flat = self._bucket()
         views = torch.split(flat, self._sizes)
         pipelined = (len(self._works) > 1 and hasattr(optimizer, "step_ranges")
                      and all(self._aliases(p, v) for p, v in zip(self.params, views)))
         if not pipelined:
             self.all_reduce_mean()
-            optimizer.step()
+            optimizer.step(**kw)
             return
         works, self._works = self._works, []
         n = self.params[0].shape[0]
@@ -360,7 +363,7 @@ class GradAllReduce:
             if not self._avg:
                 for v in views:
                     v.view(n, -1)[lo:hi].div_(world)
-        optimizer.step_ranges([(lo, hi) for lo, hi, _ in works], before)
+        optimizer.step_ranges([(lo, hi) for lo, hi, _ in works], before, **kw)
 
     def _wait(self, ws) -> None:
         """Make the current stream wait for one range's collective(s): torch

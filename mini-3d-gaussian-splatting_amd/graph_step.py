@@ -68,6 +68,10 @@ class GraphedStep:
 
     def __init__(self, renderer, camera, model, settings, cotangents: Sequence[torch.Tensor],
                  optimizer=None, eager_step: Optional[Callable[[], None]] = None, fused_adam: bool = False):
+        if getattr(getattr(model, "config", None), "visible_adam", False):
+            raise ValueError("GraphedStep replays the dense Adam update: the model's configuration asks for "
+                             "visible_adam, which the replayed step does not apply -- train through "
+                             "GaussianTrainer, or turn visible_adam off")
         if not getattr(model, "_gs_fused_covariance", False):
             raise ValueError("GraphedStep renders this package's GaussianModel (raw scaling / rotation)")
         if optimizer is not None and not hasattr(optimizer, "param_out"):

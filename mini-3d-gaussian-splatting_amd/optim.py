@@ -6,6 +6,13 @@ group.  This optimizer keeps the same per-group hyper-parameters and state
 layout ('step', 'exp_avg', 'exp_avg_sq' per parameter) but updates every
 tensor in a single gs_adam_step launch.
 Parameters without .grad are skipped, as torch does.
+
+Visibility-gated step (gsplat's visible_adam / SelectiveAdam, the sparse Adam
+of Taming 3DGS): step(visible=mask) updates the rows mask marks and leaves the
+parameters and both moments of every other row bit for bit, whatever their
+gradients hold -- one gs_adam_step_rows launch.  The step counts (and so the
+bias corrections) advance as without the mask: they are per tensor, not per
+row.
 """
 from __future__ import annotations
 
@@ -85,6 +92,57 @@ class FusedAdam(torch.optim.Optimizer):
                                             N.ptr(out) + 4 * off if out is not None else None)
                 N.check(lib.gs_adam_step(C.byref(a), stream), "gs_adam_step")
 
+    def _check_visible(self, visible) -> None:
+        """ValueError unless `visible` is a contiguous [N] bool / uint8 tensor
+        on the parameters' device with N = dim 0 of every parameter that has
+        a gradient, and no such parameter has a set_output (before anything
+        is launched or counted)."""
+        if not isinstance(visible, torch.Tensor) or visible.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("visible must be a bool or uint8 tensor, got "
+                             f"{getattr(visible, 'dtype', type(visible).__name__)}")
+        if visible.dim() != 1 or not visible.is_contiguous():
+            raise ValueError(f"visible must be a contiguous [N] mask, got shape {tuple(visible.shape)} "
+                             f"stride {tuple(visible.stride())}")
+        n = visible.shape[0]
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.device != visible.device:
+                    raise ValueError(f"visible is on {visible.device}, a parameter on {p.device}")
+                if p.dim() < 1 or p.shape[0] != n:
+                    raise ValueError(f"visible marks {n} rows, a parameter with a gradient has shape "
+                                     f"{tuple(p.shape)}")
+                if p in self.param_out:
+                    raise ValueError("visible does not combine with set_output parameters (gs_adam_step_rows "
+                                     "updates in place)")
+
+    @staticmethod
+    def _launch_rows(batches, visible, lo=None, hi=None):
+        """_launch through gs_adam_step_rows: rows [lo, hi) (all when lo is
+        None) of every tensor, the mask offset by lo."""
+        if not batches:
+            return
+        lib = N.load()
+        stream = N.stream_ptr()
+        n = visible.shape[0]
+        r0, r1 = (0, n) if lo is None else (min(lo, n), min(hi, n))
+        for (b1, b2, eps), ds in batches.items():
+            for i in range(0, len(ds), N.GS_ADAM_MAX_TENSORS):
+                chunk = ds[i:i + N.GS_ADAM_MAX_TENSORS]
+                a = N.GsAdamRowsArgs()
+                a.rows, a.row_mask = r1 - r0, N.ptr(visible) + r0
+                ad = a.adam
+                ad.num_tensors, ad.beta1, ad.beta2, ad.eps = len(chunk), b1, b2, eps
+                ad.one_minus_beta1, ad.one_minus_beta2 = 1.0 - b1, 1.0 - b2  # (in double, rounded once)
+                for k, (p, m, v, g, rows, lr, bc1, bc2s, _) in enumerate(chunk):
+                    cols = p.numel() // max(rows, 1)
+                    off = r0 * cols
+                    a.cols[k] = max(cols, 1)
+                    ad.t[k] = N.GsAdamTensor(N.ptr(p) + 4 * off, N.ptr(m) + 4 * off, N.ptr(v) + 4 * off,
+                                             N.ptr(g) + 4 * off, (r1 - r0) * cols, lr, bc1, bc2s, None)
+                N.check(lib.gs_adam_step_rows(C.byref(a), stream), "gs_adam_step_rows")
+
     def zero_grad(self, set_to_none: bool = True) -> None:
         """Optimizer.zero_grad without its profiler annotation (host time
         the small configurations are bound by); same semantics."""
@@ -124,17 +182,33 @@ class FusedAdam(torch.optim.Optimizer):
         return out
 
     @torch.no_grad()
-    def step(self, closure=None):
-        """One Adam step over every parameter with a gradient.  The launch
+    def step(self, closure=None, visible=None):
+        """One Adam step over every parameter with a gradient.  visible: a [N]
+        bool / uint8 mask on the parameters' device -- only the rows it marks
+        are updated (every parameter with a gradient must have N rows); None:
+        the dense step, as follows.  The launch
         descriptors are kept between steps and only the per-step fields
         (gradient address, lr, bias corrections) rewritten while the
         parameters, moments and outputs stay where they were.  torch's
         profiler annotation is not run (step is marked hooked, see below);
         registered step pre / post hooks (per optimizer or global) are, when
         there are any (checking costs two dict tests)."""
+        if visible is not None:
+            if self._hooks_registered():
+                return self._hooked(self._step_visible, (closure,), {"visible": visible})
+            return self._step_visible(closure, visible=visible)
         if self._hooks_registered():
             return self._hooked(self._step, (closure,), {})
         return self._step(closure)
+
+    def _step_visible(self, closure=None, visible=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._check_visible(visible)
+        self._launch_rows(self._begin(), visible)
+        return loss
 
     def _step(self, closure=None):
         loss = None
@@ -200,22 +274,29 @@ class FusedAdam(torch.optim.Optimizer):
     step.hooked = True
 
     @torch.no_grad()
-    def step_ranges(self, ranges, before=None):
+    def step_ranges(self, ranges, before=None, visible=None):
         """The same update as step() (Adam is elementwise: bit-identical),
         launched over row ranges [lo, hi) of every parameter in turn; before(k),
         when given, runs before range k is queued -- the data-parallel
         reducer makes the stream wait for range k's all-reduce there, so
-        range k's update overlaps the reductions of the ranges after it."""
+        range k's update overlaps the reductions of the ranges after it.
+        visible: as step(); range k reads the mask from row lo on (the ranges
+        are arbitrary, nothing is rounded to the kernel's row blocks)."""
+        if visible is not None:
+            self._check_visible(visible)
         if self._hooks_registered():
-            return self._hooked(self._step_ranges, (ranges, before), {})
-        return self._step_ranges(ranges, before)
+            return self._hooked(self._step_ranges, (ranges, before), {} if visible is None else {"visible": visible})
+        return self._step_ranges(ranges, before, visible=visible)
 
-    def _step_ranges(self, ranges, before=None):
+    def _step_ranges(self, ranges, before=None, visible=None):
         batches = self._begin()
         for k, (lo, hi) in enumerate(ranges):
             if before is not None:
                 before(k)
-            self._launch(batches, lo, hi)
+            if visible is None:
+                self._launch(batches, lo, hi)
+            else:
+                self._launch_rows(batches, visible, lo, hi)
 
 
 # --------------------------------------------------------------------------
@@ -307,8 +388,13 @@ class GaussianOptimizer:
             {"params": [g._rotation], "lr": c.rotation_lr},
         ])  # torch.optim.Adam defaults, as optimizer.py:109
 
-    def step(self) -> None:
-        self.optimizer.step()
+    def step(self, visible=None) -> None:
+        """The Adam step; visible: the [N] mask of the rows to update
+        (FusedAdam.step), None: every row."""
+        if visible is None:
+            self.optimizer.step()
+        else:
+            self.optimizer.step(visible=visible)
 
     def zero_grad(self) -> None:
         self.optimizer.zero_grad(set_to_none=True)

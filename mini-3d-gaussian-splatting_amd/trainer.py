@@ -17,14 +17,19 @@ clone / prune, position noise every iteration).  With filter_3d every render
 smoothing filter, recomputed from all training cameras every
 filter_3d_interval iterations and whenever the rows change.  With lambda_distortion > 0 the
 loss gains, from distortion_from_iter on, lambda_distortion times the mean
-depth distortion of the view (render(depth_distortion=True)).  Nothing in a step reads a value
+depth distortion of the view (render(depth_distortion=True)).  With visible_adam the Adam step
+updates only the Gaussians the step's view saw (the render's visibility_filter); every other row
+keeps its parameters and both moments bit for bit.  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.
 
 Data parallel: with torch.distributed initialised,
 rank r renders camera perm[(i * world + r) mod n] at iteration i; every rank
 applies the same averaged gradients and the same densification (the
 gradients are identical after the all-reduce and the clone jitter is seeded
-by the iteration), so the replicas stay bit-identical.
+by the iteration), so the replicas stay bit-identical.  With visible_adam the
+step's mask is the union of the ranks' visibility (one MAX all-reduce of the N
+mask bytes, issued after the render and before the backward's gradient
+ranges): the averaged gradient is non-zero for the rows any rank saw.
 """
 from __future__ import annotations
 
@@ -159,6 +164,7 @@ class GaussianTrainer:
             if c.distortion_near_far is not None:
                 extra["distortion_near_far"] = c.distortion_near_far
         out = self.renderer.render(camera, g, self._settings(camera), **extra)
+        visible = self._visible_mask(out) if c.visible_adam else None
         target = camera._image
         total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
         if distort:
@@ -166,14 +172,14 @@ class GaussianTrainer:
         total.backward()
         opt.update_learning_rate(self.iteration)
         if c.densify_criterion == "mcmc":
-            self._mcmc_update()
+            self._mcmc_update(visible)
             return {"loss": total.detach(), "l1": l1, "dssim": dssim}
         if self._dist is not None:
             # mean all-reduce, then Adam; pipelined per Gaussian range when the
             # backward handed its rows over in ranges (GS_ALLREDUCE_CHUNKS)
-            self._reducer.reduce_and_step(opt.optimizer)
+            self._reducer.reduce_and_step(opt.optimizer, visible=visible)
         else:
-            opt.step()
+            opt.step(visible=visible)
         info = opt.densify_and_prune(self.iteration, self.scene_extent, dist=self._dist)
         if info is not None:
             self._reducer = None
@@ -186,19 +192,37 @@ class GaussianTrainer:
             self.last_compact = self.compact()
         return {"loss": total.detach(), "l1": l1, "dssim": dssim}
 
-    def _mcmc_update(self) -> None:
+    def _visible_mask(self, out) -> torch.Tensor:
+        """config.visible_adam: the step's row mask, the render's
+        visibility_filter as [N] uint8; data parallel the union over the
+        ranks (every rank renders another camera, and the averaged gradient
+        is non-zero for the rows any of them saw): one MAX all-reduce of the
+        mask bytes through the process group, as the density statistics are
+        reduced, so every rank steps the same rows."""
+        mask = out["visibility_filter"].view(torch.uint8)
+        if self._dist is not None:
+            mask = mask.clone()
+            self._dist.all_reduce(mask, op=self._dist.ReduceOp.MAX)
+        return mask
+
+    def _mcmc_update(self, visible: Optional[torch.Tensor] = None) -> None:
         """The rest of a step with densify_criterion "mcmc", after the backward:
         [gradient mean], the regularisers' gradients, Adam, on a refinement
         iteration relocate_and_grow, and the position noise.  Every seed is
         the iteration's, and the regulariser is added after the mean (the
         same bits on every rank), so replicas and resumed runs stay
         bit-identical.  The bucket is dropped only when tensors were replaced:
-        once N is at mcmc_cap_max nothing moves again."""
+        once N is at mcmc_cap_max nothing moves again.  visible (config.
+        visible_adam): the Adam step updates the marked rows only, so the
+        regularisers' gradients on the rows the view did not see are ignored
+        with the rest of those rows' gradients (the opacity and scale
+        penalties act on a Gaussian in the steps that see it); relocation and
+        the position noise are not gated."""
         opt, c = self.optimizer, self.config
         if self._dist is not None:
             self._reducer.all_reduce_mean()
         opt.mcmc_regularize()
-        opt.step()
+        opt.step(visible=visible)
         info = opt.relocate_and_grow(self.iteration)
         if info is not None:
             self.last_densify = info
