@@ -20,7 +20,10 @@ loss gains, from distortion_from_iter on, lambda_distortion times the mean
 depth distortion of the view (render(depth_distortion=True)).  With visible_adam the Adam step
 updates only the Gaussians the step's view saw (the render's visibility_filter); every other row
 keeps its parameters and both moments bit for bit.  Nothing in a step reads a value
-back to the host; losses are logged every log_interval iterations.
+back to the host; losses are logged every log_interval iterations.  A
+checkpoint holds what a later step reads -- parameters, Adam moments and step
+counts, the 3D filter, the "screen" statistics accumulated since the last
+densification -- so a resumed run is the uninterrupted one, bit for bit.
 
 Data parallel: with torch.distributed initialised,
 rank r renders camera perm[(i * world + r) mod n] at iteration i; every rank
@@ -33,6 +36,7 @@ ranges): the averaged gradient is non-zero for the rows any rank saw.
 """
 from __future__ import annotations
 
+import json
 import os
 from typing import Dict, List, Optional
 
@@ -320,15 +324,53 @@ class GaussianTrainer:
         if self.filter_3d is not None:
             for name, v in self.filter_3d.state().items():
                 tensors[f"filter_3d.{name}"] = v.contiguous()
+        if self._density_stats_in_checkpoint():
+            for name, v in self._density_state().items():
+                tensors[f"density.{name}"] = v.contiguous()
+        meta = {"iteration": str(iteration), "active_sh_degree": str(self.gaussians.active_sh_degree)}
+        if self.last_densify is not None:
+            meta["last_densify"] = json.dumps(self.last_densify)
         path = self._ckpt_path(iteration)
-        save_file({k: v.cpu() for k, v in tensors.items()}, path,
-                  metadata={"iteration": str(iteration), "active_sh_degree": str(self.gaussians.active_sh_degree)})
+        save_file({k: v.cpu() for k, v in tensors.items()}, path, metadata=meta)
         return path
+
+    def _density_stats_in_checkpoint(self) -> bool:
+        """The "screen" criterion's statistics are state between two
+        densifications and go into the checkpoint (keys written only when the
+        option is on, as the filter's are).  Not data parallel: each rank's
+        statistics are its own partial sums until the densification's
+        all-reduce, and one file read by every rank would count them world
+        times; such a run resumes with zeros."""
+        if self.config.densify_criterion != "screen":
+            return False
+        return self._dist is None or self._dist.get_world_size() <= 1
+
+    def _density_state(self) -> Dict[str, torch.Tensor]:
+        st = self.gaussians.density_stats
+        out = {"grad_accum": st.grad_accum, "denom": st.denom, "max_radii": st.max_radii}
+        if self.config.densify_absgrad and st.abs_accum is not None:
+            out["abs_accum"] = st.abs_accum
+        return out
+
+    def _load_density_state(self, t: Dict[str, torch.Tensor]) -> None:
+        """Copy the density.* tensors of a checkpoint into the model's fresh
+        (zero) statistics; a buffer the file does not hold stays zero (an older
+        checkpoint, or one of a run without densify_absgrad), and abs_accum is
+        ignored without densify_absgrad."""
+        st = self.gaussians.density_stats
+        for name, dst in self._density_state().items():
+            src = t.get(f"density.{name}")
+            if src is None:
+                continue
+            if tuple(src.shape) != (st.n,) or src.dtype != torch.float32:
+                raise ValueError(f"the checkpoint's density.{name} must be fp32 [{st.n}], got {src.dtype} "
+                                 f"{tuple(src.shape)}")
+            dst.copy_(src)
 
     def load_checkpoint(self, iteration: int) -> None:
         from safetensors import safe_open
         path = self._ckpt_path(iteration)
-        dev = self.gaussians._xyz.device if self.gaussians is not None else torch.device("cuda")
+        dev = self.gaussians._xyz.device if self.gaussians is not None else self._device()
         with safe_open(path, framework="pt") as f:
             t = {k: f.get_tensor(k) for k in f.keys()}
             meta = f.metadata() or {}
@@ -345,9 +387,12 @@ class GaussianTrainer:
                                                      "exp_avg_sq": t[f"adam.{name}.v"].to(dev)}
         self.iteration = int(meta.get("iteration", iteration))
         self.gaussians.active_sh_degree = int(meta.get("active_sh_degree", 0))
+        self.last_densify = json.loads(meta["last_densify"]) if "last_densify" in meta else None
         self._reducer = None
         if self._perm is None:
             self._setup_run()
+        if self._density_stats_in_checkpoint():
+            self._load_density_state(t)
         if self.config.filter_3d:
             n = self.gaussians.get_num_points()
             if "filter_3d.values" in t:

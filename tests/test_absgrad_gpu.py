@@ -530,8 +530,10 @@ def _middle(v):
 def test_trainer_densifies_on_absolute_gradients(pkg, cuda, tmp_path):
     """300 iterations of tests/test_density_training_gpu.py's scene with
     densify_absgrad: densification runs, PSNR rises, and a run resumed from
-    the checkpoint of iteration 200 (right after a densification: the
-    statistics are zeros in both) equals the uninterrupted one bit for bit."""
+    the checkpoint of iteration 200 equals the uninterrupted one bit for bit.
+    (200 is right after a densification, where the statistics are zeros: the
+    one kind of iteration at which a checkpoint that lost them could not
+    show.  tests/test_resume_gpu.py resumes where they are live.)"""
     from scene_util import load_scene, write_scene_files
     write_scene_files(tmp_path, 12, 64)
     ds = load_scene(pkg, tmp_path, cuda, 64)

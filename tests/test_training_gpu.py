@@ -51,6 +51,8 @@ def test_trainer_learns_and_checkpoints(pkg, cuda, tmp_path):
     assert math.isclose(tr2.validate()["psnr"], after["psnr"], rel_tol=1e-6)
     # resuming trains on: the run state (cameras, scene extent) is rebuilt by
     # load_checkpoint, and the resumed run takes the same steps as the original
+    # (saved at the last iteration, after densification has ended: a resume
+    # inside a densification interval is tests/test_resume_gpu.py's)
     assert tr2.scene_extent == tr.scene_extent and tr2._perm is not None
     tr.train(5)
     tr2.train(5)
