@@ -1183,6 +1183,78 @@ typedef struct gs_filter3d_args {
 gs_status gs_filter3d_forward(const gs_filter3d_args *a, gs_stream_t stream);
 gs_status gs_filter3d_backward(const gs_filter3d_args *a, gs_stream_t stream);
 
+/* ---- Normal consistency (2DGS, Huang et al. 2024, Sec. 5) ------------------
+ * The other half of the geometry regularisation, next to the depth distortion:
+ * each Gaussian's normal, composited per pixel by the feature pass
+ * (N_r = sum_i c_i n_i), should agree with the normal of the surface the depth
+ * map implies.  Two per-Gaussian kernels make the normals and their gradient,
+ * two per-pixel kernels the error and its gradient; the blend in between is
+ * gs_blend_features_*.  Stream ordered, no allocation, no atomics, no host
+ * sync, the same bits every run; every check below returns
+ * GS_ERR_INVALID_ARG before any HIP call. */
+
+/* gs_gaussian_normals_forward / _backward: one thread per Gaussian.
+ *   k   = argmin_k scaling[k], the first among equals (the flat axis)
+ *   q^  = q / max(|q|, 1e-12), q = rotation row (w, x, y, z), un-normalised
+ *   n_w = column k of R(q^)               (gs_gaussians' rotation matrix)
+ *   n_c = Rv n_w,  p_c = Rv xyz + t       (view = [Rv | t], row-major 3x4)
+ *   normals = n_c . p_c > 0 ? -n_c : n_c  (faces the camera; an exact 0 keeps the sign)
+ * computed in double from the fp32 inputs and rounded once.  The backward
+ * stores (does not add) d_rotation from g_normals through the flip sign, Rv,
+ * column k and the normalisation; the axis choice and the flip are piecewise
+ * constant, so scaling, xyz and the view receive nothing.  n == 0 is GS_OK
+ * with nothing launched.  The forward reads rotation, scaling, xyz, view and
+ * writes normals; the backward reads g_normals too and writes d_rotation. */
+typedef struct gs_gaussian_normals_args {
+  int32_t n;
+  const float *rotation;  /* [n,4] raw (w, x, y, z) */
+  const float *scaling;   /* [n,3] log */
+  const float *xyz;       /* [n, xyz_stride] */
+  int64_t xyz_stride;     /* floats between rows, >= 3 */
+  float view[12];         /* row-major 3x4, world -> camera */
+  float *normals;         /* [n,3] camera space (forward) */
+  const float *g_normals; /* [n,3] (backward) */
+  float *d_rotation;      /* [n,4] (backward) */
+} gs_gaussian_normals_args;
+gs_status gs_gaussian_normals_forward(const gs_gaussian_normals_args *a, gs_stream_t stream);
+gs_status gs_gaussian_normals_backward(const gs_gaussian_normals_args *a, gs_stream_t stream);
+
+/* gs_normal_consistency_forward / _backward: one thread per pixel.  With the
+ * renderer's conventions (integer pixel coordinates, y_pix = -fy Y / Z + cy),
+ * N = normals, D = depth, A = alpha:
+ *   r(x,y) = ((x - cx) / fx, -(y - cy) / fy, 1),  P = D r
+ *   interior pixels (1 <= x <= W-2, 1 <= y <= H-2):
+ *     dx = P(x+1,y) - P(x-1,y),  dy = P(x,y+1) - P(x,y-1),  m = dx x dy
+ *     n_d = m / |m| where |m| is finite and > 1e-20, else 0
+ *   border pixels: n_d = 0
+ *   error = 1 - A (N . n_d)
+ * (2DGS's 1 - sum rend_normal * surf_normal * alpha.detach(); dx x dy faces
+ * the camera: negative z for a fronto-parallel plane).  In fp32, the
+ * differences formed as (D+ - D-) r + (D+ + D-) (1/fx, 0, 0) and
+ * (D+ - D-) r + (D+ + D-) (0, -1/fy, 0).  surface_normals receives n_d, or is
+ * NULL.  The backward stores, from g_error,
+ *   d_normals = -A g_error n_d
+ *   g_n = -A g_error N,  g_m = (g_n - n_d (n_d . g_n)) / |m|  (0 where n_d is 0)
+ *   g_dx = dy x g_m,  g_dy = g_m x dx
+ *   d_depth(x,y) = r(x,y) . [g_dx(x-1,y) - g_dx(x+1,y) + g_dy(x,y-1) - g_dy(x,y+1)]
+ * (0 for a neighbour that is not interior) as a gather; alpha is a weight and
+ * receives no gradient.  width, height >= 1 (height <= 262140); fx, fy finite
+ * and not 0; cx, cy finite. */
+typedef struct gs_normal_consistency_args {
+  int32_t width, height;
+  float fx, fy, cx, cy;
+  const float *normals;   /* [3,H,W] */
+  const float *depth;     /* [H,W] */
+  const float *alpha;     /* [H,W] */
+  float *error;           /* [H,W] (forward) */
+  float *surface_normals; /* [3,H,W], or NULL (forward) */
+  const float *g_error;   /* [H,W] (backward) */
+  float *d_normals;       /* [3,H,W] (backward) */
+  float *d_depth;         /* [H,W] (backward) */
+} gs_normal_consistency_args;
+gs_status gs_normal_consistency_forward(const gs_normal_consistency_args *a, gs_stream_t stream);
+gs_status gs_normal_consistency_backward(const gs_normal_consistency_args *a, gs_stream_t stream);
+
 /* ---- Frame entry points: the stages above in one call per direction -------
  * gs_render_forward runs what GaussianRenderer.render does (renderer.py:31-114)
  * -- projection + culling, depth sort, binning, tile sort, ranges, blend --

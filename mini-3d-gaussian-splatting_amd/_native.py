@@ -359,6 +359,17 @@ class GsFilter3dArgs(C.Structure):
                 ("d_opacity", _vp)]
 
 
+class GsGaussianNormalsArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("rotation", _vp), ("scaling", _vp), ("xyz", _vp), ("xyz_stride", C.c_int64),
+                ("view", C.c_float * 12), ("normals", _vp), ("g_normals", _vp), ("d_rotation", _vp)]
+
+
+class GsNormalConsistencyArgs(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("normals", _vp), ("depth", _vp), ("alpha", _vp),
+                ("error", _vp), ("surface_normals", _vp), ("g_error", _vp), ("d_normals", _vp), ("d_depth", _vp)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -375,6 +386,8 @@ EXPORTS = (
     "gs_blend_backward_abs", "gs_gather_abs_partials", "gs_density_accumulate_abs",
     "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
     "gs_adam_step_rows",
+    "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
+    "gs_normal_consistency_forward", "gs_normal_consistency_backward",
 )
 
 _lib = None
@@ -456,6 +469,10 @@ def _declare(lib):
     lib.gs_filter3d_accumulate.argtypes = [P(GsFilter3dRateArgs), _vp]
     lib.gs_filter3d_forward.argtypes = [P(GsFilter3dArgs), _vp]
     lib.gs_filter3d_backward.argtypes = [P(GsFilter3dArgs), _vp]
+    lib.gs_gaussian_normals_forward.argtypes = [P(GsGaussianNormalsArgs), _vp]
+    lib.gs_gaussian_normals_backward.argtypes = [P(GsGaussianNormalsArgs), _vp]
+    lib.gs_normal_consistency_forward.argtypes = [P(GsNormalConsistencyArgs), _vp]
+    lib.gs_normal_consistency_backward.argtypes = [P(GsNormalConsistencyArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
@@ -464,7 +481,8 @@ def _declare(lib):
               "gs_blend_distortion_backward", "gs_mcmc_sample", "gs_mcmc_relocate", "gs_mcmc_noise",
               "gs_mcmc_regularize", "gs_blend_backward_abs", "gs_gather_abs_partials",
               "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
-              "gs_adam_step_rows"):
+              "gs_adam_step_rows", "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
+              "gs_normal_consistency_forward", "gs_normal_consistency_backward"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -105,6 +105,13 @@ class TrainingConfig:
     lambda_distortion: float = 0.0
     distortion_from_iter: int = 0
     distortion_near_far: Optional[tuple] = None
+    # normal consistency (2DGS, also gsplat and RaDe-GS): once normal_from_iter iterations are done (the
+    # steps numbered above it, 2DGS's `iteration > 7000`) the step renders with normals=True and the loss
+    # gains lambda_normal * mean over the pixels of 1 - alpha (N_r . n_d), N_r the rendered normals and n_d
+    # the depth map's (normals.normal_consistency).  2DGS uses 0.05 from iteration 7000.  0 = off: the
+    # step's launches are the ones they were
+    lambda_normal: float = 0.0
+    normal_from_iter: int = 0
     # visibility-gated Adam (gsplat's visible_adam, the sparse Adam of Taming 3DGS): a step updates only the
     # Gaussians its view saw (the render's visibility_filter; data parallel: the union over the ranks' views);
     # every other row keeps its parameters and both Adam moments bit for bit instead of drifting along a
@@ -149,6 +156,12 @@ class TrainingConfig:
         it = self.distortion_from_iter
         if isinstance(it, bool) or not isinstance(it, int) or it < 0:
             raise ValueError(f"distortion_from_iter must be an integer >= 0, got {it!r}")
+        lam = float(self.lambda_normal)
+        if not (lam >= 0.0 and lam != float("inf")):
+            raise ValueError(f"lambda_normal must be finite and >= 0, got {self.lambda_normal!r}")
+        it = self.normal_from_iter
+        if isinstance(it, bool) or not isinstance(it, int) or it < 0:
+            raise ValueError(f"normal_from_iter must be an integer >= 0, got {it!r}")
         nf = self.distortion_near_far
         if nf is not None:
             ok = isinstance(nf, (tuple, list)) and len(nf) == 2 and all(isinstance(v, (int, float)) for v in nf)

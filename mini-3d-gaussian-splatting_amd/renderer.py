@@ -37,6 +37,10 @@ Differences a caller can observe (all documented in DESIGN.md):
     Gaussian with Mip-Splatting's 3D smoothing filter before the projection
     (filter3d.py); with `settings.screen_filter` the pair is its anti-aliased
     mode.
+  * `render(..., normals=True)` (not in the reference) also returns "normals",
+    the camera-space normal of every Gaussian (normals.gaussian_normals)
+    composited like a feature: the rendered half of the normal consistency
+    term (normals.normal_consistency).
   * `settings.sh_degree` (default: the model's `active_sh_degree`, else 0)
     switches on view-dependent SH colour; at 0 -- the default for the
     reference's own model and stubs -- colours are the reference's
@@ -52,6 +56,7 @@ import torch
 
 from . import _native as N
 from .filter3d import Filter3D, apply_filter_3d, check_filter_3d_variance
+from . import normals as _normals
 from .rasterizer import (CameraParams, ContributionStats, DensityStats, check_distortion_near_far,
                          check_screen_filter, rasterize)
 
@@ -157,6 +162,25 @@ def _check_filter_3d(filter_3d, gaussians, fused) -> None:
                          f"{gaussians._opacity.dtype}")
 
 
+def _check_normals(gaussians, fused, features) -> None:
+    """ValueError for a render(normals=True) that cannot be done, before any launch."""
+    if not fused:
+        raise ValueError("normals=True needs this package's GaussianModel (scaling and rotation): a model rendered "
+                         "through get_covariance has no axes to take a normal from")
+    if features is not None:
+        if not isinstance(features, torch.Tensor):
+            raise TypeError(f"features must be a tensor, got {type(features).__name__}")
+        if features.dim() != 2:
+            raise ValueError(f"features must be [N, C], got {tuple(features.shape)}")
+        n, c = int(gaussians._rotation.shape[0]), int(features.shape[1])
+        if c + 3 > N.GS_MAX_FEATURE_CHANNELS:
+            raise ValueError(f"normals=True takes three feature channels: features may have at most "
+                             f"{N.GS_MAX_FEATURE_CHANNELS - 3} (GS_MAX_FEATURE_CHANNELS - 3), got {c}")
+        if features.shape[0] != n or not features.is_floating_point() or features.device != gaussians._rotation.device:
+            raise ValueError(f"features must be floating-point [{n}, C] on {gaussians._rotation.device}, got "
+                             f"{features.dtype} {tuple(features.shape)} on {features.device}")
+
+
 class GaussianRenderer:
     """renderer.py:22-114"""
 
@@ -179,8 +203,26 @@ class GaussianRenderer:
                density_stats: Optional[DensityStats] = None,
                contribution_stats: Optional[ContributionStats] = None,
                dominant: bool = False, depth_distortion: bool = False,
-               distortion_near_far=None, filter_3d: Optional[Filter3D] = None) -> Dict[str, torch.Tensor]:
-        """filter_3d: optional Filter3D of the model's size on its device
+               distortion_near_far=None, filter_3d: Optional[Filter3D] = None,
+               normals: bool = False) -> Dict[str, torch.Tensor]:
+        """normals: the result also holds "normals", fp32 [3, H, W]: each pixel's
+        sum_i c_i n_i with the colour pass's own weights, n_i the camera-space
+        normal of Gaussian i (normals.gaussian_normals on the model's raw
+        _rotation, _scaling and _xyz: its shortest axis, facing the camera).
+        Not normalised: its length is about alpha.  The three channels ride the
+        feature pass, behind `features` when both are given (C + 3 <=
+        GS_MAX_FEATURE_CHANNELS), and the frame takes the stage path: the seven
+        standard outputs and their gradients are the same bits.  With filter_3d
+        the raw scaling still decides the axis (the filter's map is monotone in
+        every axis, so the shortest stays the shortest).  The rotation's
+        gradient arrives in two pieces, the render's and the normals', so a
+        data-parallel bucket is not written by the kernels, as with filter_3d.
+        The normals read the view as host scalars: a world_view_transform that
+        requires grad gets its gradient from every other output and none
+        through the normals.  Only this package's GaussianModel: a duck-typed
+        model is a ValueError before anything is launched.  False is the render
+        without the argument, launch for launch.
+        filter_3d: optional Filter3D of the model's size on its device
         (Mip-Splatting's 3D smoothing filter, filter3d.py).  The model's raw
         _scaling and _opacity then pass through apply_filter_3d and the
         projection reads the results: scaling' and the probability opacity'.
@@ -266,6 +308,8 @@ class GaussianRenderer:
         fused = getattr(gaussians, "_gs_fused_covariance", False)
         if filter_3d is not None:
             _check_filter_3d(filter_3d, gaussians, fused)
+        if normals:
+            _check_normals(gaussians, fused, features)
         if fused:
             # this package's GaussianModel: covariance from the raw scaling /
             # rotation and get_opacity's sigmoid are computed in the kernels;
@@ -295,7 +339,8 @@ class GaussianRenderer:
         grad_dest = None
         # (with a 3D filter the projection's scaling / opacity gradients are those of
         # the map's outputs: they must not land in the bucket as the leaves')
-        sink = getattr(gaussians, "_gs_grad_sink", None) if fused and filter_3d is None else None
+        # (with normals the rotation's gradient has a second part, from the normals' backward)
+        sink = getattr(gaussians, "_gs_grad_sink", None) if fused and filter_3d is None and not normals else None
         if sink is not None:
             # data-parallel bucket (distributed.GradAllReduce.attach): the
             # gradient kernels write straight into it when it can take them
@@ -320,7 +365,10 @@ class GaussianRenderer:
                     d["_rows_ready"], d["_chunks"] = sink.rows_ready, sink.overlap_chunks()
                 return d
         extra = dict(pose)
-        if features is not None:
+        if normals:
+            n_c = _normals.gaussian_normals(gaussians._rotation, gaussians._scaling, gaussians._xyz, wv)
+            extra["features"] = n_c if features is None else torch.cat([features.float(), n_c], dim=1)
+        elif features is not None:
             extra["features"] = features
         if density_stats is not None:
             extra["density_stats"] = density_stats
@@ -356,6 +404,12 @@ class GaussianRenderer:
         if depth_distortion:
             out["distortion"], out["median_depth"], out["median_gaussian"] = feature_image[-3:]
             feature_image = feature_image[:-3]
-        if feature_image:
+        if normals:
+            if features is None:
+                out["normals"] = feature_image[0]
+            else:
+                c = features.shape[1]
+                out["features"], out["normals"] = feature_image[0][:c], feature_image[0][c:]
+        elif feature_image:
             out["features"] = feature_image[0]
         return out

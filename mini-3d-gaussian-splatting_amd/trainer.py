@@ -17,7 +17,9 @@ clone / prune, position noise every iteration).  With filter_3d every render
 smoothing filter, recomputed from all training cameras every
 filter_3d_interval iterations and whenever the rows change.  With lambda_distortion > 0 the
 loss gains, from distortion_from_iter on, lambda_distortion times the mean
-depth distortion of the view (render(depth_distortion=True)).  With visible_adam the Adam step
+depth distortion of the view (render(depth_distortion=True)), and with lambda_normal > 0, after
+iteration normal_from_iter, lambda_normal times the mean normal consistency error of the view
+(render(normals=True), normals.normal_consistency; no state between steps).  With visible_adam the Adam step
 updates only the Gaussians the step's view saw (the render's visibility_filter); every other row
 keeps its parameters and both moments bit for bit.  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.  A
@@ -48,6 +50,7 @@ from .dataset import CameraDataset, load_dataset
 from .filter3d import Filter3D
 from .gaussian_model import GaussianModel
 from .loss import photometric_loss
+from . import normals as _normals
 from .optim import GaussianOptimizer
 from .renderer import GaussianRenderer, RenderSettings
 
@@ -167,12 +170,20 @@ class GaussianTrainer:
             extra["depth_distortion"] = True
             if c.distortion_near_far is not None:
                 extra["distortion_near_far"] = c.distortion_near_far
+        # the normal consistency term: eager too, next to the distortion; after iteration
+        # normal_from_iter (2DGS: lambda_normal if iteration > 7000 else 0)
+        normal = c.lambda_normal > 0 and self.iteration > c.normal_from_iter
+        if normal:
+            extra["normals"] = True
         out = self.renderer.render(camera, g, self._settings(camera), **extra)
         visible = self._visible_mask(out) if c.visible_adam else None
         target = camera._image
         total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
         if distort:
             total = total + c.lambda_distortion * out["distortion"].mean()
+        if normal:
+            total = total + c.lambda_normal * _normals.normal_consistency(out["normals"], out["depth"], out["alpha"],
+                                                                          camera).mean()
         total.backward()
         opt.update_learning_rate(self.iteration)
         if c.densify_criterion == "mcmc":
