@@ -12,84 +12,14 @@
 #include "gsplat_mi355x.h"
 #include "gs_internal.h"
 #include "gs_device.h"
+#include "gs_blend_device.h"
 
 namespace {
 
-#ifndef GS_DEBUG  // 1: report (printf) blend list ranges clamped to the T entries
-#define GS_DEBUG 0
-#endif
-constexpr float kAlphaStop = 0.995f;             // renderer.py:352
-// renderer.py:336 skips a pair when w = exp(-s/2) < 1e-5; decided here on
-// s: s > 2 ln(1e5).  The same decision except where exp's rounding
-// straddles 1e-5 -- the band in which any two fp32 exps (ours, torch's)
-// already disagree -- and it saves the compare on w for every evaluated
-// pair (C3: the same 9 knife-edge pixels).  Forward and backward share it.
-constexpr float kSkipS = 23.0258509f;
-// The blend kernels evaluate t = -s/2 directly: the conic coefficients are
-// staged as -Q/2 (a power-of-two scaling, exact for every product and sum of
-// the reference's s), so the skip is t < -ln(1e5), the same decision.
-constexpr float kSkipT = -0.5f * kSkipS;
-
 // torch.clamp semantics (NaN propagates)
 __device__ __forceinline__ float clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-// clamp to [0,1] as the VALU clamp output modifier (folds into the producing
-// instruction).  Equals clamp01 for every non-NaN input; NaN -> 0 instead of
-// NaN (only reachable from NaN/inf inputs).  Used on the blend's hot path.
-__device__ __forceinline__ float sat01(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, 1.f); }
 // wave-uniform "any lane" without the bool -> VGPR -> compare round trip
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-
-// exp(t) for the blend's exponent t = -s/2 (it evaluates the exp only for
-// s <= 23.1, t in [-11.6, 0]; beyond, for non-positive-definite conics, it
-// stays finite until 2^ph overflows), given t itself: the blend kernels
-// compute t from the conic staged as -Q/2 (stage_conic0/1).  ph = t log2(e)
-// rounded, 2^ph by v_exp_f32 (no range reduction or ldexp: 2^ph stays a
-// normal float here), times (1 + d) with the remainder d = t - ph ln2 in
-// natural-log units (Cody-Waite: ln2 in two parts, each fma's product exact).
-// ~1 ulp, like expf; forward and backward share it, so their decisions
-// replay bit-identically.  5 VALU per pair.  Rounds 2-5 took the remainder
-// in log2 units (ph + pl from x log2(e), then 2^ph (1 + pl ln2)) and the
-// exponent from s (x = -s/2): 6 VALU, and the same values (round 6: every one
-// of 2.6 M sampled t, emulated).  Dropping the remainder's low part instead
-// saves a VALU too, but is <= 3 ulp at t = -11.6: 12 knife-edge pixels and
-// the scaling gradient's error 5.4e-4 -> 1.2e-3 of scale (round 2).  Not taken.
-__device__ __forceinline__ float exp_blend(float t) {
-  const float ph = t * 0x1.715476p+0f;
-  const float r = __builtin_amdgcn_exp2f(ph);
-  float d = __builtin_fmaf(-ph, 0x1.62e430p-1f, t);
-  d = __builtin_fmaf(-ph, -0x1.05c610p-29f, d);
-  return __builtin_fmaf(r, d, r);
-}
-
-// A record's conic staged for the blend loops as -Q/2: t = conic_s(dx, dy,
-// h00, ho, h11) is then -s/2 exactly.
-__device__ __forceinline__ float4 stage_conic0(float4 r0) {  // (mx, my, q00, q11) -> (mx, my, h00, h11)
-  return make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
-}
-__device__ __forceinline__ float4 stage_conic1(float4 r1) {  // (qo, o, r, g) -> (ho, o, r, g)
-  return make_float4(-0.5f * r1.x, r1.y, r1.z, r1.w);
-}
-
-// s = [dx dy] Q [dx dy]^T for the blend's conic form (q00, qo = Q01+Q10,
-// q11) in the reference's unfused order (renderer.py:333).  A fused form
-// (5 operations instead of 8) was measured: with ill-conditioned conics the
-// cancellation amplifies its ~1-ulp difference into visible errors (needle
-// test: 1e-2 image error), so the reference's rounding is kept.
-__device__ __forceinline__ float conic_s(float dx, float dy, float q00, float qo, float q11) {
-  return ((dx * dx) * q00 + (qo * dx) * dy) + (dy * dy) * q11;
-}
-
-// ======================================================== blend fwd =======
-// Cells: a tile of edge L (GaussianRenderer.tile_size) is covered from its
-// origin by QX x QX cells of 8x8 pixels, QX = ceil(L/8) (edge cells clipped
-// to the tile); a wave renders one cell, lane l its pixel (l&7, l>>3), and
-// blends the tile's whole list (renderer.py:302-319).  L = 16: the tile's
-// four 8x8 quadrants.
-struct CellGeom {
-  int L, QX;
-  __device__ explicit CellGeom(int tile_size) : L(tile_size), QX((tile_size + 7) >> 3) {}
-  __device__ int cells() const { return QX * QX; }
-};
 
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll
@@ -145,34 +75,7 @@ __device__ __forceinline__ bool cell_hit(float mx, float my, float q00, float qo
   return fminf(fminf(e0, e1), fminf(e2, e3)) <= L;
 }
 
-// Workgroup b -> (tile, cell) and the tile's list range: b, b+8, b+16, ...
-// share an XCD (round-robin dispatch; placement is for speed only), so the Q
-// cells of a tile read its records through one L2.  Grid: ceil(tiles / 8) *
-// 8 Q.  Position (b / 8 / Q) * 8 + b % 8 is the tile.  tile >= num_tiles:
-// padding, no range.  (A heaviest-first dispatch order saved 4-9 us per
-// launch at C3 but cost ~14 us to sort: tools/variants/README.md.)  The
-// range is clamped to the T list entries (scalar, free): a corrupt ranges
-// table cannot make the kernels read past sorted_gauss; a -DGS_DEBUG=1 build
-// also reports any range it had to clamp.
-__device__ __forceinline__ void cell_tile(uint32_t b, int ncell, const uint32_t *ranges, int ntiles, uint32_t T,
-                                          int &tile, int &quad, uint32_t &start, uint32_t &end) {
-  const uint32_t grp = b >> 3;
-  const uint32_t q = (uint32_t)ncell;
-  quad = (int)(grp % q);
-  tile = (int)((grp / q) * 8u + (b & 7u));
-  start = end = 0u;
-  if (tile < ntiles) {
-    start = __builtin_amdgcn_readfirstlane(ranges[2 * tile]);
-    end = __builtin_amdgcn_readfirstlane(ranges[2 * tile + 1]);
-#if GS_DEBUG
-    if ((end > T || start > end) && threadIdx.x == 0)
-      printf("gsplat: tile %d range [%u, %u) outside the %u entries, clamped\n", tile, start, end, T);
-#endif
-    end = min(end, T);
-    start = min(start, end);
-  }
-}
-
+// ======================================================== blend fwd =======
 // Forward blend, one 64-lane workgroup per (tile, 8x8 cell), lane = pixel
 // (compact footprints keep the per-pair branches coherent).  The cells of a
 // tile run independently (no barrier): each stages its own batches of 64
@@ -242,8 +145,7 @@ __global__ __launch_bounds__(kWave) void k_blend_fwd(gs_blend_fwd_args a) {
     d[2] = n2;
     const bool hit = b + (uint32_t)lane < end && cell_hit(n0.x, n0.y, n0.z, n1.x, n0.w, (float)x0, (float)y0);
     const unsigned long long mw = __builtin_amdgcn_ballot_w64(hit);
-    unsigned long long m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(mw >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)mw);
+    unsigned long long m = uniform_u64(mw);
     // the next batch's records in flight while this one composites
     // (fetching the ids a batch earlier, so that this is one round trip, was
     // measured: no change, profiles/r03/experiments.md)
@@ -480,10 +382,7 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
   // liveness word wd of this quadrant, cut at wstop (bits past it were never written)
   auto live_word = [&](uint32_t wd) -> unsigned long long {
     const unsigned long long w = wd == 0 ? w0 : (lw ? lw[wd] : ~0ull);
-    // (readfirstlane returns int: widen through uint32_t, never sign-extend)
-    const unsigned long long m =
-        ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w);
+    const unsigned long long m = uniform_u64(w);
     const uint32_t rem = wstop - 64u * wd;
     return rem < 64u ? m & ((1ull << rem) - 1ull) : m;
   };
@@ -746,15 +645,6 @@ __global__ __launch_bounds__(kWave) void k_blend_bwd(gs_blend_bwd_args a, BwdSta
   }
 }
 
-int cells_per_tile(int tile_size) {
-  const int qx = (tile_size + GS_QUAD - 1) / GS_QUAD;
-  return qx * qx;
-}
-
-bool tiles_match(const gs_camera &c, int tiles_x, int tiles_y) {
-  return tiles_x == (int)div_up(c.image_width, c.tile_size) && tiles_y == (int)div_up(c.image_height, c.tile_size);
-}
-
 // gs_blend_backward's checks, cell batch and launch; abs_grads: NULL, or the
 // [T, G, 2] buffer of gs_blend_backward_abs (the kAbs instantiations)
 gs_status blend_backward(const gs_blend_bwd_args *a, float *abs_grads, const char *what, gs_stream_t stream) {
@@ -767,18 +657,11 @@ gs_status blend_backward(const gs_blend_bwd_args *a, float *abs_grads, const cha
       !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", what);
   if (a->num_pairs < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs", what);
-  const int cells = cells_per_tile(a->cam.tile_size);
   gs_blend_bwd_args b = *a;
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
-                "[0, gs_tile_quads(tile_size))", what);
+  long long blocks;
+  if (const gs_status st = cell_batch(b, what, &blocks)) return st;
   hipStream_t s = (hipStream_t)stream;
-  const int num_tiles = b.tiles_x * b.tiles_y;
-  if (num_tiles <= 0) return GS_OK;
-  const long long blocks = (long long)div_up(num_tiles, 8) * 8LL * b.cell_count;
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", what);
-  const bool t16 = b.cam.tile_size == GS_DEFAULT_TILE && b.cell_count == cells;
+  const bool t16 = b.cam.tile_size == GS_DEFAULT_TILE && b.cell_count == cells_per_tile(b.cam.tile_size);
   if (abs_grads) {
     const BwdAbs ab{reinterpret_cast<float2 *>(abs_grads)};
     if (t16)
@@ -824,9 +707,9 @@ gs_status gs_blend_forward(const gs_blend_fwd_args *a, gs_stream_t stream) {
   if (a->num_pairs < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs", "gs_blend_forward");
   hipStream_t s = (hipStream_t)stream;
   const bool t16 = a->cam.tile_size == GS_DEFAULT_TILE;
-  const long long cblocks = (long long)div_up((long long)a->tiles_x * a->tiles_y, 8) * 8LL * cells_per_tile(a->cam.tile_size);
-  // (a launch's work-items, workgroups x 64, must stay below 2^32)
-  if (cblocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", "gs_blend_forward");
+  long long cblocks;
+  if (!cell_grid(a->tiles_x, a->tiles_y, cells_per_tile(a->cam.tile_size), &cblocks))
+    return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", "gs_blend_forward");
   if (a->pair_counts)
     k_blend_fwd<true, false><<<(unsigned)cblocks, kWave, 0, s>>>(*a);
   else if (t16)

@@ -1,10 +1,11 @@
 // gs_device.h -- what more than one stage of the render path uses: the block
-// geometry, the block scans, the DPP lane sums, the under-aligned vector
-// types, the counter-based normals, the one Adam update, and the host-side
-// camera check.  Everything is in an anonymous namespace (each .hip file is
-// its own translation unit and code object); a helper with a single user
-// lives in that user's file.  Not part of the C ABI.  Wave size is 64
-// everywhere.
+// geometry, the block scans, the DPP lane sums (oct_sum, and lanes_sum of the
+// gathers), the under-aligned vector types, the counter-based normals, the
+// one Adam update, and the host-side camera check.  Everything is in an
+// anonymous namespace (each .hip file is its own translation unit and code
+// object); a helper with a single user lives in that user's file, and what
+// only the blend family shares -- the blend's decisions, the cell geometry --
+// in gs_blend_device.h.  Not part of the C ABI.  Wave size is 64 everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -133,6 +134,24 @@ __device__ __forceinline__ float oct_sum(float v) {
   // (empty asm: keeps the last add next to its DPP move, where the two fold
   // into one v_add_f32_dpp, instead of being sunk into the storing lane's branch)
   asm volatile("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ float quad_sum(float v) {
+  v += dpp_row<0xB1>(v);  // quad_perm [1,0,3,2]
+  v += dpp_row<0x4E>(v);  // quad_perm [2,3,0,1]
+  asm volatile("" : "+v"(v));
+  return v;
+}
+// Sum over the LPG lanes of a gather's Gaussian (8, 4, 2 or 1), oct_sum's steps
+template <int LPG>
+__device__ __forceinline__ float lanes_sum(float v) {
+  if constexpr (LPG == 8) return oct_sum(v);
+  if constexpr (LPG == 4) return quad_sum(v);
+  if constexpr (LPG == 2) {
+    v += dpp_row<0xB1>(v);
+    asm volatile("" : "+v"(v));
+    return v;
+  }
   return v;
 }
 

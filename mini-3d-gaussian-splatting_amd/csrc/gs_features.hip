@@ -9,68 +9,22 @@
 // No blend kernel here decides anything of its own: all replay the colour
 // forward (k_blend_fwd, gs_blend.hip) over the state it saved -- ranges,
 // sorted_gauss, records, cell_neval, live_bits -- with the operations
-// k_blend_bwd replays it with.  The helpers that form a decision (exp_blend,
-// conic_s, the -Q/2 staging, the s skip, A = A + c, T1 = 1 - A) are restated
-// here from gs_blend.hip operation for operation: each .hip file is its own
-// translation unit, built with the same flags (no contraction), so the same
-// source gives the same bits.
+// k_blend_bwd replays it with.  Everything that forms a decision (exp_blend,
+// conic_s, the -Q/2 staging, the s skip, the weight, A = A + c, T1 = 1 - A,
+// the stop) is gs_blend_device.h's one copy, which gs_blend.hip is built from
+// too, with the same flags (no contraction): the same source gives the same
+// bits.  Two walks own the rest of a replay -- word_walk for the forward-type
+// passes, group_walk for those that reduce per entry -- so a pass states its
+// payload, its accumulation and its stores, and nothing of the decision.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gsplat_mi355x.h"
 #include "gs_internal.h"
 #include "gs_device.h"
+#include "gs_blend_device.h"
 
 namespace {
-
-constexpr float kAlphaStop = 0.995f;             // renderer.py:352
-constexpr float kSkipS = 23.0258509f;            // renderer.py:336 on s: s > 2 ln(1e5)
-constexpr float kSkipT = -0.5f * kSkipS;         // ... on t = -s/2
-
-__device__ __forceinline__ float sat01(float v) { return __builtin_amdgcn_fmed3f(v, 0.f, 1.f); }
-
-// gs_blend.hip's exp_blend (Cody-Waite around v_exp_f32), unchanged
-__device__ __forceinline__ float exp_blend(float t) {
-  const float ph = t * 0x1.715476p+0f;
-  const float r = __builtin_amdgcn_exp2f(ph);
-  float d = __builtin_fmaf(-ph, 0x1.62e430p-1f, t);
-  d = __builtin_fmaf(-ph, -0x1.05c610p-29f, d);
-  return __builtin_fmaf(r, d, r);
-}
-
-// t = -s/2 for a conic staged as -Q/2, in the reference's unfused order (renderer.py:333)
-__device__ __forceinline__ float conic_s(float dx, float dy, float q00, float qo, float q11) {
-  return ((dx * dx) * q00 + (qo * dx) * dy) + (dy * dy) * q11;
-}
-
-struct CellGeom {
-  int L, QX;
-  __device__ explicit CellGeom(int tile_size) : L(tile_size), QX((tile_size + 7) >> 3) {}
-  __device__ int cells() const { return QX * QX; }
-};
-
-// Workgroup b -> (tile, cell of the launch's ncell) and the tile's list range,
-// clamped to the T entries (k_blend_fwd's placement: b, b + 8, ... share an XCD).
-__device__ __forceinline__ void cell_tile(uint32_t b, int ncell, const uint32_t *ranges, int ntiles, uint32_t T,
-                                          int &tile, int &quad, uint32_t &start, uint32_t &end) {
-  const uint32_t grp = b >> 3;
-  const uint32_t q = (uint32_t)ncell;
-  quad = (int)(grp % q);
-  tile = (int)((grp / q) * 8u + (b & 7u));
-  start = end = 0u;
-  if (tile < ntiles) {
-    start = __builtin_amdgcn_readfirstlane(ranges[2 * tile]);
-    end = __builtin_amdgcn_readfirstlane(ranges[2 * tile + 1]);
-    end = min(end, T);
-    start = min(start, end);
-  }
-}
-
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long w) {
-  // (readfirstlane returns int: widen through uint32_t, never sign-extend)
-  return ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
-         (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w);
-}
 
 // A cell's replay: its tile, pixel and the words of its liveness bitmap, cut
 // at the cell's last evaluated entry (bits past it were never written).
@@ -88,108 +42,323 @@ struct Replay {
   }
 };
 
-// false: nothing to replay (padding workgroup is reported through r.tile)
-__device__ __forceinline__ bool replay_setup(Replay &r, const gs_camera &cam, int tiles_x, int tiles_y, int ncell,
-                                             int cell0, const uint32_t *ranges, uint32_t T,
-                                             const uint32_t *cell_neval, const uint64_t *live_bits,
-                                             int64_t live_words) {
-  const CellGeom cg(cam.tile_size);
+// The replay of this workgroup's cell, one of the ncell cells from cell0 of
+// its tile, over the forward's state in a.  false: nothing to replay (a
+// padding workgroup is reported through r.tile)
+template <class Args>
+__device__ __forceinline__ bool replay_setup(Replay &r, const Args &a, int ncell, int cell0) {
+  const CellGeom cg(a.cam.tile_size);
+  const uint32_t T = (uint32_t)a.num_pairs;
   int qb;
   uint32_t end;
-  cell_tile(blockIdx.x, ncell, ranges, tiles_x * tiles_y, T, r.tile, qb, r.start, end);
+  cell_tile(blockIdx.x, ncell, a.ranges, a.tiles_x * a.tiles_y, T, r.tile, qb, r.start, end);
   r.wstop = r.nwords = 0u;
   r.inside = false;
   r.lw = nullptr;
-  if (r.tile >= tiles_x * tiles_y) return false;
+  if (r.tile >= a.tiles_x * a.tiles_y) return false;
   r.quad = cell0 + qb;
   const int lane = threadIdx.x;
-  r.tx = (uint32_t)(r.tile % tiles_x);
-  r.ty = (uint32_t)(r.tile / tiles_x);
+  r.tx = (uint32_t)(r.tile % a.tiles_x);
+  r.ty = (uint32_t)(r.tile / a.tiles_x);
   const int cx0 = (r.quad % cg.QX) * 8, cy0 = (r.quad / cg.QX) * 8;  // the cell in its tile
   r.x0 = (int)r.tx * cg.L + cx0;
   r.y0 = (int)r.ty * cg.L + cy0;
   r.px = r.x0 + (lane & 7);
   r.py = r.y0 + (lane >> 3);
-  r.inside = cx0 + (lane & 7) < cg.L && cy0 + (lane >> 3) < cg.L && r.px < cam.image_width && r.py < cam.image_height;
+  r.inside =
+      cx0 + (lane & 7) < cg.L && cy0 + (lane >> 3) < cg.L && r.px < a.cam.image_width && r.py < a.cam.image_height;
   if (r.start >= end) return false;
   // the cell's last evaluated entry (never past the list, whatever the word holds)
-  r.wstop = min((uint32_t)__builtin_amdgcn_readfirstlane(cell_neval[(size_t)r.tile * cg.cells() + r.quad]),
+  r.wstop = min((uint32_t)__builtin_amdgcn_readfirstlane(a.cell_neval[(size_t)r.tile * cg.cells() + r.quad]),
                 end - r.start);
   r.nwords = (r.wstop + 63u) >> 6;
-  if (live_bits)
-    r.lw = reinterpret_cast<const unsigned long long *>(live_bits) + (size_t)r.quad * live_words + r.start / 64u +
+  if (a.live_bits)
+    r.lw = reinterpret_cast<const unsigned long long *>(a.live_bits) + (size_t)r.quad * a.live_words + r.start / 64u +
            (uint32_t)r.tile;
   return r.wstop != 0u;
 }
 
-// ====================================================== feature fwd =======
-// One 64-lane workgroup per (tile, 8x8 cell) and chunk (grid y), lane = pixel.
+// ======================================================== word walk =======
+// The walk of the forward-type replays (k_feat_fwd, k_dist_fwd), lane = pixel.
 // Per 64-entry word of the cell's liveness bitmap: the live entries' records
 // and payloads are gathered lane-parallel (the next word's meanwhile, in
-// registers), staged in LDS and walked in bit order as broadcasts.  The
-// weight is k_blend_fwd's: skips folded in (a skipped pair gets ai = 0, hence
-// c = +0), c = (1 - A) ai, A = A + c.
+// registers), staged in s_rec (3 float4 per lane) and walked in bit order as
+// broadcasts.  The weight is k_blend_fwd's: skips folded in (a skipped pair
+// gets ai = 0, hence c = +0), c = (1 - A) ai, A = A + c.  A pass gives
+//   payload(gid)        the float4 it carries for Gaussian gid,
+//   entry(payload, c, A) its accumulation, A the sum before the entry,
+// and gets back the pixel's A after the last one.
+template <class Args, class Payload, class Entry>
+__device__ __forceinline__ float word_walk(const Replay &r, const Args &a, float4 *s_rec, Payload payload,
+                                           Entry entry) {
+  const int lane = threadIdx.x;
+  const uint32_t ngauss = (uint32_t)a.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  const float fx = (float)r.px, fy = (float)r.py;
+  float A = 0.f, T1 = 1.f;
+  bool run = r.inside;  // A < 0.995 so far; lanes outside the tile or image never run
+  float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, nf = n0;
+  auto fetch = [&](uint32_t wd, unsigned long long m) {
+    if ((m >> lane) & 1ull) {
+      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+      n0 = recs[3 * (size_t)gid];
+      n1 = recs[3 * (size_t)gid + 1];
+      nf = payload(gid);
+    }
+  };
+  unsigned long long mcur = r.live_word(0);
+  fetch(0, mcur);
+  for (uint32_t wd = 0; wd < r.nwords; ++wd) {
+    // (this wave's reads of the previous word precede these writes in its in-order LDS queue)
+    if ((mcur >> lane) & 1ull) {  // per entry: (mx my h00 h11) (ho o - -) payload, h = -q/2
+      const float4 h1 = stage_conic1(n1);
+      s_rec[3 * lane] = stage_conic0(n0);
+      s_rec[3 * lane + 1] = make_float4(h1.x, h1.y, 0.f, 0.f);
+      s_rec[3 * lane + 2] = nf;
+    }
+    const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
+    fetch(wd + 1u, mnext);  // in flight while this word composites
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
+    unsigned long long m = mcur;
+    while (m) {
+      const uint32_t bit = (uint32_t)__builtin_ctzll(m);
+      m &= m - 1ull;
+      const float4 c0 = s_rec[3 * bit], c1 = s_rec[3 * bit + 1], fv = s_rec[3 * bit + 2];
+      const float dx = fx - c0.x, dy = fy - c0.y;
+      const float t = conic_s(dx, dy, c0.z, c1.x, c0.w);  // -s/2 (:333)
+      const float c = pair_weight(t, c1.y, T1, run).c;
+      entry(fv, c, A);
+      const bool go = blend_advance(A, T1, c);
+      run = run && go;
+    }
+    asm volatile("" ::: "memory");
+    mcur = mnext;
+  }
+  return A;
+}
+
+// ======================================================= group walk =======
+// The walk of the replays that reduce over a cell's pixels per entry
+// (k_feat_bwd, k_dist_bwd, k_contrib): k_blend_bwd's two phases without its
+// tuning (no simple-entry fast path), per group of up to kBwdGroup live
+// entries of a word:
+//  A (pixel-parallel), per entry: replay the pixel's chain, and the pass puts
+//    what it sums into its group buffers' row kk;
+//  B (entry-parallel): lanes 8j..8j+7 sum entry j's 64 pixels -- lane 8j + x
+//    takes column x -- and reduce with 3 DPP steps.
+constexpr int kBwdGroup = 8;
+constexpr int kBwdLanes = kWave / kBwdGroup;
+constexpr int kBwdRow = kWave + 8;  // rows padded to 72 float2: no bank conflict between a half's rows
+
+// One entry of a pixel's chain, as phase A gets it
+struct ChainStep {
+  PairWeight p;   // the weight c and what formed it
+  float A0, T0;   // A and the transmittance 1 - A before the entry
+  float A1, T1;   // ... and after it
+  bool term;      // A1 >= 0.995: nothing behind this entry
+};
+
+// The staged record of a group entry: (mx my h00 h11) (ho o . .), h = -q/2,
+// then per layout the payload p and the entry's gradient slot.
+struct Rec3 {  // (mx my h00 h11) (ho o p0 p1) (p2 p3 slot -)
+  static constexpr int kF4 = 3;
+  static __device__ __forceinline__ void pack(float4 *c, float4 r0, float4 r1, float4 p, uint32_t slot) {
+    const float4 h1 = stage_conic1(r1);
+    c[0] = stage_conic0(r0);
+    c[1] = make_float4(h1.x, h1.y, p.x, p.y);
+    c[2] = make_float4(p.z, p.w, __uint_as_float(slot), 0.f);
+  }
+  static __device__ __forceinline__ uint32_t slot(const float4 *rec) { return __float_as_uint(rec[2].z); }
+};
+struct Rec2 {  // (mx my h00 h11) (ho o slot p0)
+  static constexpr int kF4 = 2;
+  static __device__ __forceinline__ void pack(float4 *c, float4 r0, float4 r1, float4 p, uint32_t slot) {
+    const float4 h1 = stage_conic1(r1);
+    c[0] = stage_conic0(r0);
+    c[1] = make_float4(h1.x, h1.y, __uint_as_float(slot), p.x);
+  }
+  static __device__ __forceinline__ uint32_t slot(const float4 *rec) { return __float_as_uint(rec[1].z); }
+};
+
+// A pass gives the layout Rec of s_wrec (kBwdGroup records) and
+//   payload(gid, r2)      the float4 it stages for Gaussian gid (r2: its third record),
+//   phase_a(kk, rec, st)  entry kk of the group for this pixel: rec its staged record, st its ChainStep,
+//   phase_b(k)            the group's k entries reduced and stored, their records at s_wrec positions 0 .. k - 1.
+template <class Rec, class Args, class Payload, class PhaseA, class PhaseB>
+__device__ __forceinline__ void group_walk(const Replay &r, const Args &a, float4 *s_wrec, Payload payload,
+                                           PhaseA phase_a, PhaseB phase_b) {
+  const int lane = threadIdx.x;
+  const uint32_t ngauss = (uint32_t)a.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  const float fx = (float)r.px, fy = (float)r.py;
+  float A = 0.f, T1 = 1.f;
+  // `run` is the forward's "A < 0.995 before this entry", carried from the
+  // previous entry's own test; lanes outside the tile or image never run
+  bool run = r.inside;
+  float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, rp = r0;
+  auto fetch = [&](uint32_t wd, unsigned long long m) {
+    if ((m >> lane) & 1ull) {
+      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+      r0 = recs[3 * (size_t)gid];
+      r1 = recs[3 * (size_t)gid + 1];
+      r2 = recs[3 * (size_t)gid + 2];
+      rp = payload(gid, r2);
+    }
+  };
+  unsigned long long mcur = r.live_word(0);
+  fetch(0, mcur);
+  for (uint32_t wd = 0; wd < r.nwords; ++wd) {
+    const bool mine = (mcur >> lane) & 1ull;
+    // packed: the live entry of rank k (bit order) at position k of its group
+    const uint32_t rank =
+        __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
+    // (the conic staged as -Q/2: phase A computes t = -s/2; phase B undoes it)
+    float4 c[Rec::kF4];
+    Rec::pack(c, r0, r1, rp, entry_slot(r2, r.tx, r.ty));
+    const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
+    fetch(wd + 1u, mnext);  // in flight while this word replays
+    unsigned long long m = mcur;
+    uint32_t kb = 0;  // packed position of the group's first entry
+    while (m) {
+      int k = 0;
+      // stage the group (ranks kb .. kb + kBwdGroup - 1; the previous group's
+      // reads came before these writes in this wave's in-order LDS queue)
+      if (mine && rank - kb < (uint32_t)kBwdGroup) {
+#pragma unroll
+        for (int i = 0; i < Rec::kF4; ++i) s_wrec[Rec::kF4 * (rank - kb) + i] = c[i];
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
+#pragma unroll
+      for (int kk = 0; kk < kBwdGroup; ++kk) {
+        if (kk > 0 && !m) break;
+        m &= m - 1ull;
+        const float4 *rec = s_wrec + Rec::kF4 * kk;
+        const float4 r0v = rec[0], r1v = rec[1];
+        const float dx = fx - r0v.x, dy = fy - r0v.y;
+        const float tq = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
+        ChainStep st;
+        st.p = pair_weight(tq, r1v.y, T1, run);
+        st.A0 = A;
+        st.T0 = T1;
+        st.term = !blend_advance(A, T1, st.p.c);
+        st.A1 = A;
+        st.T1 = T1;
+        phase_a(kk, rec, st);
+        run = run && !st.term;
+        k = kk + 1;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
+      phase_b(k);
+      kb += (uint32_t)k;
+    }
+    mcur = mnext;
+  }
+}
+
+// dL/dalpha_i = T_i (X_i + (P_i - K) / T_{i+1}) of a chain step, PG = P_i - K
+// after it, through the two clamps of the weight: (dop, +-c) for phase B,
+// the sign bit of c flagging exp(-s/2) > 1 (the weight clamp then blocks dL/ds).
+__device__ __forceinline__ float2 step_grad(const ChainStep &st, float X, float PG) {
+  // both arms computed, then a select: no divergent branch per entry
+  const float inv = __builtin_amdgcn_rcpf(st.T1);  // v_rcp_f32 (1 ulp): a gradient factor, no decision
+  const float d_live = __builtin_fmaf(inv, PG, X);
+  // the terminating contributor has nothing behind it
+  const float dal = st.T0 * (st.term ? X : d_live);
+  // (PairWeight: the clamps pass the gradient where ai == u and w == e)
+  const float g = (st.p.ai == st.p.u) ? dal * st.p.w : 0.f;
+  const float dop = (st.p.c > 0.f) ? g : 0.f;
+  const float cw = (st.p.w == st.p.e) ? st.p.c : -st.p.c;  // c == +0 when skipped
+  return make_float2(dop, cw);
+}
+
+// Phase B of the two backward replays, Rec3 records and (dop, +-c) in s_dc:
+// entry j's geometric sums over this lane's column and the entry's flagged
+// 40-B partial {dmu_x, dmu_y, dQ00, dQ01, dQ11, d_opacity, tail(j)}.  The
+// pass gives row(j, pp, cw), its own sums over pixel pp (phase A's lane) with
+// |c| = cw, and tail(j), components 6 to 9 (called by all the entry's lanes:
+// it may oct_sum).
+template <class Args, class Row, class Tail>
+__device__ __forceinline__ void phase_b_geometry(const Replay &r, const Args &a, const float4 *s_wrec,
+                                                 const float2 (*s_dc)[kBwdRow], int k, Row row, Tail tail) {
+  const int lane = threadIdx.x;
+  const int j = lane / kBwdLanes, col = lane % kBwdLanes;
+  if (j < k) {
+    const float4 *rec = s_wrec + 3 * j;
+    const float4 ia = rec[0];                                    // mx my h00 h11 (h = -q/2)
+    const float2 ib = make_float2(rec[1].x, rec[1].y);           // ho o
+    const float q00 = -2.f * ia.z, q11 = -2.f * ia.w, qo = -2.f * ib.x;  // (exact)
+    const uint32_t slot = Rec3::slot(rec);
+    const float hop = -0.5f * ib.y;
+    // this lane's pixels (x0 + col, y0 + row): dx = bx, dy = by + (row - rc).
+    // The row moments are taken about the column row nearest the mean
+    // (clamped), always: about row 0 the dy^2 sum of a Gaussian with
+    // sigma_y << 1 px cancels (by^2 S0 + 2 by Soy + Soyy with |by| up to 7
+    // for a result of ~sigma_y^2 S0), as k_blend_bwd's comment measures.
+    const float bx = (float)(r.x0 + col) - ia.x;
+    const float rc = __builtin_amdgcn_fmed3f(__builtin_rintf(ia.y - (float)r.y0), 0.f, (float)(kBwdGroup - 1));
+    float S0 = 0.f, Soy = 0.f, Soyy = 0.f, g5 = 0.f;
+#pragma unroll
+    for (int rw = 0; rw < kBwdGroup; ++rw) {
+      const int pp = col + 8 * rw;  // phase A's lane of that pixel
+      const float2 dc = s_dc[j][pp];
+      const float dop = dc.x, cs = dc.y;
+      // dL/ds = hop dop: none where the weight clamp bound (sign bit of c)
+      // or the pair was skipped (dop = 0 then)
+      const float ds = cs > 0.f ? dop : 0.f;
+      const float wr = (float)rw - rc;  // exact: small integers
+      S0 += ds;
+      Soy = __builtin_fmaf(ds, wr, Soy);
+      Soyy = __builtin_fmaf(ds, wr * wr, Soyy);
+      g5 += dop;
+      row(j, pp, fabsf(cs));
+    }
+    S0 *= hop;
+    Soy *= hop;
+    Soyy *= hop;
+    const float by = (float)r.y0 + rc - ia.y;
+    // sums of ds dx, ds dy, ds dx^2, ds dx dy, ds dy^2 over the lane's column
+    float Sx = bx * S0, Sy = __builtin_fmaf(by, S0, Soy);
+    float g2 = bx * Sx, g3 = bx * Sy;
+    float g4 = __builtin_fmaf(by, __builtin_fmaf(by, S0, 2.f * Soy), Soyy);
+    Sx = oct_sum(Sx); Sy = oct_sum(Sy); g2 = oct_sum(g2); g3 = oct_sum(g3); g4 = oct_sum(g4);
+    g5 = oct_sum(g5);
+    const float4 t = tail(j);
+    if (col == 0) {
+      // dmu = -(2 q00 Sx + qo Sy, qo Sx + 2 q11 Sy)
+      const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
+      const size_t sq = (size_t)slot * (uint32_t)a.cell_count + (uint32_t)(r.quad - a.cell_begin);
+      if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+        float *out = a.pair_grads + sq * GS_PARTIAL_STRIDE;  // (dense 40-B partials, 8-B aligned: f4_u8)
+        *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2, g3};
+        *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, t.x, t.y};
+        *reinterpret_cast<f2_u8 *>(out + 8) = f2_u8{t.z, t.w};
+        a.slot_live[sq] = 1;
+      }
+    }
+  }
+}
+
+// ====================================================== feature fwd =======
+// One 64-lane workgroup per (tile, 8x8 cell) and chunk (grid y): the word
+// walk with the chunk's four channels as the payload.
 __global__ __launch_bounds__(kWave) void k_feat_fwd(gs_feature_fwd_args a) {
   __shared__ float4 s_rec[kWave * 3];  // per entry: (mx my h00 h11) (ho o - -) (f0 f1 f2 f3), h = -q/2
   Replay r;
   const CellGeom cg(a.cam.tile_size);
-  const bool any = replay_setup(r, a.cam, a.tiles_x, a.tiles_y, cg.cells(), 0, a.ranges, (uint32_t)a.num_pairs,
-                                a.cell_neval, a.live_bits, a.live_words);
+  const bool any = replay_setup(r, a, cg.cells(), 0);
   if (r.tile >= a.tiles_x * a.tiles_y) return;
-  const int lane = threadIdx.x;
   const uint32_t chunk = blockIdx.y;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
-  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)chunk * ngauss;
+  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)chunk * (uint32_t)a.num_gaussians;
   float f0 = 0.f, f1 = 0.f, f2 = 0.f, f3 = 0.f;
-  if (any) {
-    const float fx = (float)r.px, fy = (float)r.py;
-    float A = 0.f, T1 = 1.f;
-    bool run = r.inside;  // A < 0.995 so far; lanes outside the tile or image never run
-    float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, nf = n0;
-    auto fetch = [&](uint32_t wd, unsigned long long m) {
-      if ((m >> lane) & 1ull) {
-        const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
-        n0 = recs[3 * (size_t)gid];
-        n1 = recs[3 * (size_t)gid + 1];
-        nf = feat[gid];
-      }
-    };
-    unsigned long long mcur = r.live_word(0);
-    fetch(0, mcur);
-    for (uint32_t wd = 0; wd < r.nwords; ++wd) {
-      // (this wave's reads of the previous word precede these writes in its in-order LDS queue)
-      if ((mcur >> lane) & 1ull) {
-        s_rec[3 * lane] = make_float4(n0.x, n0.y, -0.5f * n0.z, -0.5f * n0.w);
-        s_rec[3 * lane + 1] = make_float4(-0.5f * n1.x, n1.y, 0.f, 0.f);
-        s_rec[3 * lane + 2] = nf;
-      }
-      const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
-      fetch(wd + 1u, mnext);  // in flight while this word composites
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
-      unsigned long long m = mcur;
-      while (m) {
-        const uint32_t bit = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1ull;
-        const float4 c0 = s_rec[3 * bit], c1 = s_rec[3 * bit + 1], fv = s_rec[3 * bit + 2];
-        const float dx = fx - c0.x, dy = fy - c0.y;
-        const float t = conic_s(dx, dy, c0.z, c1.x, c0.w);  // -s/2 (:333)
-        const bool lv = run && !(t < kSkipT);                // the :336 skip, decided on s
-        const float w = sat01(exp_blend(t));                 // :334
-        const float ai = lv ? sat01(c1.y * w) : 0.f;         // :339
-        const float c = T1 * ai;                             // :343-344 (T1 = 1 - A)
-        f0 = __builtin_fmaf(c, fv.x, f0);
-        f1 = __builtin_fmaf(c, fv.y, f1);
-        f2 = __builtin_fmaf(c, fv.z, f2);
-        f3 = __builtin_fmaf(c, fv.w, f3);
-        A = A + c;
-        T1 = 1.f - A;
-        run = run && A < kAlphaStop;                         // the :352 break
-      }
-      asm volatile("" ::: "memory");
-      mcur = mnext;
-    }
-  }
+  if (any)
+    word_walk(
+        r, a, s_rec, [&](uint32_t gid) { return feat[gid]; },
+        [&](const float4 &fv, float c, float) {
+          f0 = __builtin_fmaf(c, fv.x, f0);
+          f1 = __builtin_fmaf(c, fv.y, f1);
+          f2 = __builtin_fmaf(c, fv.z, f2);
+          f3 = __builtin_fmaf(c, fv.w, f3);
+        });
   if (!r.inside) return;
   const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
   const size_t p = (size_t)r.py * a.cam.image_width + r.px;
@@ -201,32 +370,19 @@ __global__ __launch_bounds__(kWave) void k_feat_fwd(gs_feature_fwd_args a) {
 }
 
 // ====================================================== feature bwd =======
-// k_blend_bwd's two phases over one chunk's payload, without its tuning (no
-// simple-entry fast path, the row moments always recentred):
-//  A (pixel-parallel), per live entry: replay the pixel's chain and put
-//    (dop, c) into a group buffer; the sign bit of c flags exp(-s/2) > 1 (the
-//    weight clamp then blocks dL/ds).
-//  B (entry-parallel), per chunk of up to kBwdGroup live entries: lanes
-//    8j..8j+7 sum entry j's 64 pixels -- lane 8j + x takes column x -- into
-//    the 10 gradient values and reduce them with 3 DPP steps.
-constexpr int kBwdGroup = 8;
-constexpr int kBwdLanes = kWave / kBwdGroup;
-constexpr int kBwdRow = kWave + 8;  // rows padded to 72 float2: no bank conflict between a half's rows
-
-__global__ __launch_bounds__(kWave) void k_feat_bwd(gs_feature_bwd_args a) {
+// The group walk over one chunk's payload: phase A puts (dop, c) into the
+// group buffer, phase B adds the four channel sums to the geometric ones.
+// (At most 6 waves per SIMD, what the kernel ran at with its own loop, 76
+// VGPRs: allocated down to 72 for a seventh wave it measured 3 to 9 us slower
+// per launch at C3, as k_blend_bwd did at 7.)
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 6))) void k_feat_bwd(gs_feature_bwd_args a) {
   __shared__ float2 s_dc[kBwdGroup][kBwdRow];  // per group entry and pixel: (dop, c)
   __shared__ float4 s_pg[kWave];               // per pixel: dL/dout of the chunk's four channels
   __shared__ float2 s_wrec[kBwdGroup * 6];     // the group's records: (mx my h00 h11) (ho o f0 f1) (f2 f3 slot -)
   Replay r;
-  const int ncell = a.cell_count;
-  if (!replay_setup(r, a.cam, a.tiles_x, a.tiles_y, ncell, a.cell_begin, a.ranges, (uint32_t)a.num_pairs,
-                    a.cell_neval, a.live_bits, a.live_words))
-    return;
-  const int qb = r.quad - a.cell_begin;  // the cell's partial group
+  if (!replay_setup(r, a, a.cell_count, a.cell_begin)) return;
   const int lane = threadIdx.x;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
-  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)a.chunk * ngauss;
+  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)a.chunk * (uint32_t)a.num_gaussians;
   // the pixel's cotangents and outputs of this chunk (channels past C: zero;
   // lanes outside read pixel 0, unused)
   const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
@@ -242,179 +398,39 @@ __global__ __launch_bounds__(kWave) void k_feat_bwd(gs_feature_bwd_args a) {
     oF[k] = has ? o : 0.f;
   }
   s_pg[lane] = make_float4(gF[0], gF[1], gF[2], gF[3]);
-  const float fx = (float)r.px, fy = (float)r.py;
   // dL/dalpha_i = T_i (X_i + (P_i - K) / T_{i+1}): PG = P - K carried as one
   // running sum (a gradient factor, no decision), P starts at 0 (no background)
   const float K = (gF[0] * oF[0] + gF[1] * oF[1]) + (gF[2] * oF[2] + gF[3] * oF[3]);
   float PG = -K;
-  float A = 0.f, T1 = 1.f;
-  bool run = r.inside;
-  float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, rf = r0;
-  auto fetch = [&](uint32_t wd, unsigned long long m) {
-    if ((m >> lane) & 1ull) {
-      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
-      r0 = recs[3 * (size_t)gid];
-      r1 = recs[3 * (size_t)gid + 1];
-      r2 = recs[3 * (size_t)gid + 2];
-      rf = feat[gid];
-    }
-  };
-  // Phase B over a group: its k live entries, staged at s_wrec positions 0 .. k - 1.
-  auto phase_b = [&](int k) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
-    const int j = lane / kBwdLanes, col = lane % kBwdLanes;
-    if (j < k) {
-      const uint32_t e = (uint32_t)j;
-      const float4 ia = reinterpret_cast<const float4 *>(s_wrec)[3 * e];  // mx my h00 h11 (h = -q/2)
-      const float2 ib = s_wrec[6 * e + 2];                                // ho o
-      const float q00 = -2.f * ia.z, q11 = -2.f * ia.w, qo = -2.f * ib.x;  // (exact)
-      const uint32_t slot = __float_as_uint(s_wrec[6 * e + 5].x);
-      const float hop = -0.5f * ib.y;
-      // this lane's pixels (x0 + col, y0 + row): dx = bx, dy = by + (row - rc).
-      // The row moments are taken about the column row nearest the mean
-      // (clamped), always: about row 0 the dy^2 sum of a Gaussian with
-      // sigma_y << 1 px cancels (by^2 S0 + 2 by Soy + Soyy with |by| up to 7
-      // for a result of ~sigma_y^2 S0), as k_blend_bwd's comment measures.
-      const float bx = (float)(r.x0 + col) - ia.x;
-      const float rc = __builtin_amdgcn_fmed3f(__builtin_rintf(ia.y - (float)r.y0), 0.f, (float)(kBwdGroup - 1));
-      float S0 = 0.f, Soy = 0.f, Soyy = 0.f, g5 = 0.f, g6 = 0.f, g7 = 0.f, g8 = 0.f, g9 = 0.f;
-#pragma unroll
-      for (int row = 0; row < kBwdGroup; ++row) {
-        const int pp = col + 8 * row;  // phase A's lane of that pixel
-        const float2 dc = s_dc[j][pp];
-        const float dop = dc.x, cs = dc.y;
-        const float4 pg = s_pg[pp];
-        // dL/ds = hop dop: none where the weight clamp bound (sign bit of c)
-        // or the pair was skipped (dop = 0 then)
-        const float ds = cs > 0.f ? dop : 0.f;
-        const float cw = fabsf(cs);
-        const float wr = (float)row - rc;  // exact: small integers
-        S0 += ds;
-        Soy = __builtin_fmaf(ds, wr, Soy);
-        Soyy = __builtin_fmaf(ds, wr * wr, Soyy);
-        g5 += dop;
-        g6 = __builtin_fmaf(pg.x, cw, g6);
-        g7 = __builtin_fmaf(pg.y, cw, g7);
-        g8 = __builtin_fmaf(pg.z, cw, g8);
-        g9 = __builtin_fmaf(pg.w, cw, g9);
-      }
-      S0 *= hop;
-      Soy *= hop;
-      Soyy *= hop;
-      const float by = (float)r.y0 + rc - ia.y;
-      // sums of ds dx, ds dy, ds dx^2, ds dx dy, ds dy^2 over the lane's column
-      float Sx = bx * S0, Sy = __builtin_fmaf(by, S0, Soy);
-      float g2 = bx * Sx, g3 = bx * Sy;
-      float g4 = __builtin_fmaf(by, __builtin_fmaf(by, S0, 2.f * Soy), Soyy);
-      Sx = oct_sum(Sx); Sy = oct_sum(Sy); g2 = oct_sum(g2); g3 = oct_sum(g3); g4 = oct_sum(g4);
-      g5 = oct_sum(g5); g6 = oct_sum(g6); g7 = oct_sum(g7); g8 = oct_sum(g8); g9 = oct_sum(g9);
-      if (col == 0) {
-        // dmu = -(2 q00 Sx + qo Sy, qo Sx + 2 q11 Sy)
-        const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
-        const size_t sq = (size_t)slot * (uint32_t)ncell + (uint32_t)qb;
-        if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
-          float *out = a.pair_grads + sq * GS_PARTIAL_STRIDE;  // (dense 40-B partials, 8-B aligned: f4_u8)
-          *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2, g3};
-          *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, g6, g7};
-          *reinterpret_cast<f2_u8 *>(out + 8) = f2_u8{g8, g9};
-          a.slot_live[sq] = 1;
-        }
-      }
-    }
-  };
-  unsigned long long mcur = r.live_word(0);
-  fetch(0, mcur);
-  for (uint32_t wd = 0; wd < r.nwords; ++wd) {
-    // word 10 of a live record becomes the entry's gradient slot (the
-    // Gaussian's first slot + this tile's index in its rectangle)
-    const bool mine = (mcur >> lane) & 1ull;
-    const uint32_t info = __float_as_uint(r2.w);
-    const uint32_t slot = __float_as_uint(r2.z) + (r.ty - ((info >> 12) & 0xFFFu)) * ((info >> 24) + 1u) +
-                          (r.tx - (info & 0xFFFu));
-    // packed: the live entry of rank k (bit order) at position k of its group
-    const uint32_t rank =
-        __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
-    // (the conic staged as -Q/2: phase A computes t = -s/2; phase B undoes it)
-    const float4 c0 = make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
-    const float4 c1 = make_float4(-0.5f * r1.x, r1.y, rf.x, rf.y);
-    const float4 c2 = make_float4(rf.z, rf.w, __uint_as_float(slot), 0.f);
-    const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
-    fetch(wd + 1u, mnext);  // in flight while this word replays
-    unsigned long long m = mcur;
-    uint32_t kb = 0;  // packed position of the group's first entry
-    while (m) {
-      int k = 0;
-      // stage the group (ranks kb .. kb + kBwdGroup - 1; the previous group's
-      // reads came before these writes in this wave's in-order LDS queue)
-      if (mine && rank - kb < (uint32_t)kBwdGroup) {
-        float4 *d = reinterpret_cast<float4 *>(&s_wrec[6 * (rank - kb)]);
-        d[0] = c0;
-        d[1] = c1;
-        d[2] = c2;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
-      const char *cb = reinterpret_cast<const char *>(s_wrec);
-#pragma unroll
-      for (int kk = 0; kk < kBwdGroup; ++kk) {
-        if (kk > 0 && !m) break;
-        m &= m - 1ull;
-        const float4 r0v = reinterpret_cast<const float4 *>(cb + 48 * kk)[0];
-        const float4 r1v = reinterpret_cast<const float4 *>(cb + 48 * kk)[1];
-        const float2 f23 = reinterpret_cast<const float2 *>(cb + 48 * kk)[4];
-        const float dx = fx - r0v.x, dy = fy - r0v.y;
-        const float tq = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
-        // `run` is the forward's "A < 0.995 before this entry", carried from
-        // the previous entry's own test
-        const bool live = run && !(tq < kSkipT);
+  float4 *wrec = reinterpret_cast<float4 *>(s_wrec);
+  group_walk<Rec3>(
+      r, a, wrec, [&](uint32_t gid, const float4 &) { return feat[gid]; },
+      [&](int kk, const float4 *rec, const ChainStep &st) {
+        const float4 r1v = rec[1];
+        const float2 f23 = make_float2(rec[2].x, rec[2].y);
         const float X = __builtin_fmaf(gF[0], r1v.z, __builtin_fmaf(gF[1], r1v.w, __builtin_fmaf(gF[2], f23.x, gF[3] * f23.y)));
-        const float e = exp_blend(tq);
-        const float w = sat01(e);
-        const float u = r1v.y * w;
-        const float ai = sat01(u);
-        const float trans = T1;
-        // the forward's skips folded into the weight exactly as there: c is
-        // +0 for a skipped pair and > 0 for an accepted one
-        const float c = trans * (live ? ai : 0.f);
-        A = A + c;
-        PG = __builtin_fmaf(c, X, PG);
-        const bool term = !(A < kAlphaStop);
-        T1 = 1.f - A;
-        // both arms computed, then a select: no divergent branch per entry
-        const float inv = __builtin_amdgcn_rcpf(T1);  // v_rcp_f32 (1 ulp): a gradient factor, no decision
-        const float d_live = __builtin_fmaf(inv, PG, X);
-        // the terminating contributor has nothing behind it
-        const float dal = trans * (term ? X : d_live);
-        run = run && !term;
-        // u = o w >= 0, so "u in [0,1]" (the clamp passes the gradient) is ai == u;
-        // e = exp(.) >= 0, so "e in [0,1]" is w == e (both false for NaN)
-        const float g = (ai == u) ? dal * w : 0.f;
-        const float dop = (c > 0.f) ? g : 0.f;
-        const float cw = (w == e) ? c : -c;  // c == +0 when skipped
-        s_dc[kk][lane] = make_float2(dop, cw);
-        k = kk + 1;
-      }
-      phase_b(k);
-      kb += (uint32_t)k;
-    }
-    mcur = mnext;
-  }
+        PG = __builtin_fmaf(st.p.c, X, PG);
+        s_dc[kk][lane] = step_grad(st, X, PG);
+      },
+      [&](int k) {
+        float g6 = 0.f, g7 = 0.f, g8 = 0.f, g9 = 0.f;
+        phase_b_geometry(
+            r, a, wrec, s_dc, k,
+            [&](int, int pp, float cw) {
+              const float4 pg = s_pg[pp];
+              g6 = __builtin_fmaf(pg.x, cw, g6);
+              g7 = __builtin_fmaf(pg.y, cw, g7);
+              g8 = __builtin_fmaf(pg.z, cw, g8);
+              g9 = __builtin_fmaf(pg.w, cw, g9);
+            },
+            [&](int) { return make_float4(oct_sum(g6), oct_sum(g7), oct_sum(g8), oct_sum(g9)); });
+      });
 }
 
 // ========================================================== gather ========
 // k_gather_slots' walk (gs_project.hip): QL x HL lanes per Gaussian, lane
 // (h, q) adds the live partials of g's slots h, h + HL, ... for the partial
 // groups q, q + QL, ..., then the lane sums are added in the same DPP order.
-template <int LPG>
-__device__ __forceinline__ float lanes_sum(float v) {
-  if constexpr (LPG == 8) return oct_sum(v);
-  if constexpr (LPG == 4 || LPG == 2) {
-    v += dpp_row<0xB1>(v);  // quad_perm [1,0,3,2]
-    if constexpr (LPG == 4) v += dpp_row<0x4E>(v);  // quad_perm [2,3,0,1]
-    asm volatile("" : "+v"(v));
-  }
-  return v;
-}
-
 template <int QL, int HL>
 __global__ __launch_bounds__(kBlock) void k_gather_feat(gs_feature_gather_args a) {
   constexpr int LPG = QL * HL;
@@ -484,106 +500,46 @@ __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
   __shared__ float s_c[kBwdGroup][kCtbRow];  // per group entry and pixel: c
   __shared__ float4 s_wrec[kBwdGroup * 2];   // the group's records: (mx my h00 h11) (ho o slot gid)
   Replay r;
-  const int ncell = a.cell_count;
-  const bool any = replay_setup(r, a.cam, a.tiles_x, a.tiles_y, ncell, a.cell_begin, a.ranges,
-                                (uint32_t)a.num_pairs, a.cell_neval, a.live_bits, a.live_words);
+  const bool any = replay_setup(r, a, a.cell_count, a.cell_begin);
   if (r.tile >= a.tiles_x * a.tiles_y) return;
   const int lane = threadIdx.x;
   float best = 0.f;
   int best_id = -1;
-  if (any) {
-    const int qb = r.quad - a.cell_begin;  // the cell's partial group
-    const uint32_t ngauss = (uint32_t)a.num_gaussians;
-    const float4 *recs = reinterpret_cast<const float4 *>(a.records);
-    const float fx = (float)r.px, fy = (float)r.py;
-    float A = 0.f, T1 = 1.f;
-    bool run = r.inside;
-    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
-    uint32_t gcur = 0u;
-    auto fetch = [&](uint32_t wd, unsigned long long m) {
-      if ((m >> lane) & 1ull) {
-        gcur = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
-        r0 = recs[3 * (size_t)gcur];
-        r1 = recs[3 * (size_t)gcur + 1];
-        r2 = recs[3 * (size_t)gcur + 2];
-      }
-    };
-    auto phase_b = [&](int k) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
-      const int j = lane / kBwdLanes, col = lane % kBwdLanes;
-      if (j < k) {
-        float sum = 0.f, mx = 0.f, cnt = 0.f;
-#pragma unroll
-        for (int row = 0; row < kBwdGroup; ++row) {
-          const float c = s_c[j][col + 8 * row];
-          sum += c;
-          mx = fmaxf(mx, c);
-          cnt += c > 0.f ? 1.f : 0.f;
-        }
-        sum = oct_sum(sum);
-        mx = oct_max(mx);
-        cnt = oct_sum(cnt);  // (small integers: exact)
-        if (col == 0) {
-          const uint32_t slot = __float_as_uint(s_wrec[2 * j + 1].z);
-          if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
-            const size_t sq = (size_t)slot * (uint32_t)ncell + (uint32_t)qb;
-            reinterpret_cast<float4 *>(a.partials)[sq] = make_float4(sum, mx, cnt, 0.f);
-            a.slot_live[sq] = 1;
-          }
-        }
-      }
-    };
-    unsigned long long mcur = r.live_word(0);
-    fetch(0, mcur);
-    for (uint32_t wd = 0; wd < r.nwords; ++wd) {
-      // the entry's gradient slot, as k_feat_bwd forms it
-      const bool mine = (mcur >> lane) & 1ull;
-      const uint32_t info = __float_as_uint(r2.w);
-      const uint32_t slot = __float_as_uint(r2.z) + (r.ty - ((info >> 12) & 0xFFFu)) * ((info >> 24) + 1u) +
-                            (r.tx - (info & 0xFFFu));
-      const uint32_t rank =
-          __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
-      const float4 c0 = make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
-      const float4 c1 = make_float4(-0.5f * r1.x, r1.y, __uint_as_float(slot), __uint_as_float(gcur));
-      const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
-      fetch(wd + 1u, mnext);  // in flight while this word replays
-      unsigned long long m = mcur;
-      uint32_t kb = 0;  // packed position of the group's first entry
-      while (m) {
-        int k = 0;
-        // (the previous group's reads came before these writes in this wave's in-order LDS queue)
-        if (mine && rank - kb < (uint32_t)kBwdGroup) {
-          s_wrec[2 * (rank - kb)] = c0;
-          s_wrec[2 * (rank - kb) + 1] = c1;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
-#pragma unroll
-        for (int kk = 0; kk < kBwdGroup; ++kk) {
-          if (kk > 0 && !m) break;
-          m &= m - 1ull;
-          const float4 r0v = s_wrec[2 * kk], r1v = s_wrec[2 * kk + 1];
-          const float dx = fx - r0v.x, dy = fy - r0v.y;
-          const float t = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
-          const bool lv = run && !(t < kSkipT);
-          const float w = sat01(exp_blend(t));
-          const float ai = lv ? sat01(r1v.y * w) : 0.f;
-          const float c = T1 * ai;
+  if (any)
+    group_walk<Rec2>(
+        r, a, s_wrec, [](uint32_t gid, const float4 &) { return make_float4(__uint_as_float(gid), 0.f, 0.f, 0.f); },
+        [&](int kk, const float4 *rec, const ChainStep &st) {
+          const float c = st.p.c;
           if (c > best) {
             best = c;
-            best_id = (int)__float_as_uint(r1v.w);
+            best_id = (int)__float_as_uint(rec[1].w);
           }
-          A = A + c;
-          T1 = 1.f - A;
-          run = run && A < kAlphaStop;
           s_c[kk][lane] = c;
-          k = kk + 1;
-        }
-        phase_b(k);
-        kb += (uint32_t)k;
-      }
-      mcur = mnext;
-    }
-  }
+        },
+        [&](int k) {
+          const int j = lane / kBwdLanes, col = lane % kBwdLanes;
+          if (j < k) {
+            float sum = 0.f, mx = 0.f, cnt = 0.f;
+#pragma unroll
+            for (int row = 0; row < kBwdGroup; ++row) {
+              const float c = s_c[j][col + 8 * row];
+              sum += c;
+              mx = fmaxf(mx, c);
+              cnt += c > 0.f ? 1.f : 0.f;
+            }
+            sum = oct_sum(sum);
+            mx = oct_max(mx);
+            cnt = oct_sum(cnt);  // (small integers: exact)
+            if (col == 0) {
+              const uint32_t slot = Rec2::slot(s_wrec + 2 * j);
+              if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+                const size_t sq = (size_t)slot * (uint32_t)a.cell_count + (uint32_t)(r.quad - a.cell_begin);
+                reinterpret_cast<float4 *>(a.partials)[sq] = make_float4(sum, mx, cnt, 0.f);
+                a.slot_live[sq] = 1;
+              }
+            }
+          }
+        });
   if (a.dominant_id && r.inside) {
     const size_t p = (size_t)r.py * a.cam.image_width + r.px;
     a.dominant_id[p] = best_id;
@@ -670,81 +626,39 @@ __device__ __forceinline__ float4 dist_payload(float z, uint32_t gid, float kapp
   return make_float4(z, inv ? kappa / z : 1.f, inv ? 1.f / z : 1.f, __uint_as_float(gid));
 }
 
-// k_feat_fwd's walk with (z, q, r, id) as the payload.  kInv: the inverse
-// map (the linear one skips the q r factor).  "A contributor so far" is
-// A > 0 and "the median is taken" is A >= 0.5, both on the A before the entry:
-// no state of their own.
+// The word walk with (z, q, r, id) as the payload.  kInv: the inverse map
+// (the linear one skips the q r factor).  "A contributor so far" is A > 0 and
+// "the median is taken" is A >= 0.5, both on the A before the entry: no state
+// of their own.
 template <bool kInv>
 __global__ __launch_bounds__(kWave) void k_dist_fwd(gs_distortion_fwd_args a, float kappa) {
   __shared__ float4 s_rec[kWave * 3];  // per entry: (mx my h00 h11) (ho o - -) (z q r id), h = -q/2
   Replay r;
   const CellGeom cg(a.cam.tile_size);
-  const bool any = replay_setup(r, a.cam, a.tiles_x, a.tiles_y, cg.cells(), 0, a.ranges, (uint32_t)a.num_pairs,
-                                a.cell_neval, a.live_bits, a.live_words);
+  const bool any = replay_setup(r, a, cg.cells(), 0);
   if (r.tile >= a.tiles_x * a.tiles_y) return;
-  const int lane = threadIdx.x;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
   const float4 *recs = reinterpret_cast<const float4 *>(a.records);
-  float A = 0.f, S = 0.f, D = 0.f, med_z = 0.f;
+  float A = 0.f, S = 0.f, D = 0.f, med_z = 0.f, zf = 0.f, rf = 1.f;
   int med_id = -1;
-  if (any) {
-    const float fx = (float)r.px, fy = (float)r.py;
-    float T1 = 1.f, zf = 0.f, rf = 1.f;
-    bool run = r.inside;  // A < 0.995 so far; lanes outside the tile or image never run
-    float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, nf = n0;
-    auto fetch = [&](uint32_t wd, unsigned long long m) {
-      if ((m >> lane) & 1ull) {
-        const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
-        n0 = recs[3 * (size_t)gid];
-        n1 = recs[3 * (size_t)gid + 1];
-        nf = dist_payload(recs[3 * (size_t)gid + 2].y, gid, kappa);
-      }
-    };
-    unsigned long long mcur = r.live_word(0);
-    fetch(0, mcur);
-    for (uint32_t wd = 0; wd < r.nwords; ++wd) {
-      // (this wave's reads of the previous word precede these writes in its in-order LDS queue)
-      if ((mcur >> lane) & 1ull) {
-        s_rec[3 * lane] = make_float4(n0.x, n0.y, -0.5f * n0.z, -0.5f * n0.w);
-        s_rec[3 * lane + 1] = make_float4(-0.5f * n1.x, n1.y, 0.f, 0.f);
-        s_rec[3 * lane + 2] = nf;
-      }
-      const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
-      fetch(wd + 1u, mnext);  // in flight while this word composites
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
-      unsigned long long m = mcur;
-      while (m) {
-        const uint32_t bit = (uint32_t)__builtin_ctzll(m);
-        m &= m - 1ull;
-        const float4 c0 = s_rec[3 * bit], c1 = s_rec[3 * bit + 1], fv = s_rec[3 * bit + 2];
-        const float dx = fx - c0.x, dy = fy - c0.y;
-        const float t = conic_s(dx, dy, c0.z, c1.x, c0.w);  // -s/2 (:333)
-        const bool lv = run && !(t < kSkipT);                // the :336 skip, decided on s
-        const float w = sat01(exp_blend(t));                 // :334
-        const float ai = lv ? sat01(c1.y * w) : 0.f;         // :339
-        const float c = T1 * ai;                             // :343-344 (T1 = 1 - A)
-        // until the first contributor (A == 0) the reference follows the entry: m = 0, and c = +0
-        const bool have = A > 0.f;
-        zf = have ? zf : fv.x;
-        float md = fv.x - zf;
-        if constexpr (kInv) {
-          rf = have ? rf : fv.z;
-          md *= fv.y * rf;
-        }
-        D = __builtin_fmaf(c, __builtin_fmaf(md, A, -S), D);
-        S = __builtin_fmaf(c, md, S);
-        if (c > 0.f && A < 0.5f) {  // (A before this entry: the median is not taken yet)
-          med_id = (int)__float_as_uint(fv.w);
-          med_z = fv.x;
-        }
-        A = A + c;
-        T1 = 1.f - A;
-        run = run && A < kAlphaStop;                         // the :352 break
-      }
-      asm volatile("" ::: "memory");
-      mcur = mnext;
-    }
-  }
+  if (any)
+    A = word_walk(
+        r, a, s_rec, [&](uint32_t gid) { return dist_payload(recs[3 * (size_t)gid + 2].y, gid, kappa); },
+        [&](const float4 &fv, float c, float Ap) {
+          // until the first contributor (A == 0) the reference follows the entry: m = 0, and c = +0
+          const bool have = Ap > 0.f;
+          zf = have ? zf : fv.x;
+          float md = fv.x - zf;
+          if constexpr (kInv) {
+            rf = have ? rf : fv.z;
+            md *= fv.y * rf;
+          }
+          D = __builtin_fmaf(c, __builtin_fmaf(md, Ap, -S), D);
+          S = __builtin_fmaf(c, md, S);
+          if (c > 0.f && Ap < 0.5f) {  // (A before this entry: the median is not taken yet)
+            med_id = (int)__float_as_uint(fv.w);
+            med_z = fv.x;
+          }
+        });
   if (!r.inside) return;
   const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
   const size_t p = (size_t)r.py * a.cam.image_width + r.px;
@@ -766,7 +680,7 @@ __global__ __launch_bounds__(kBlock) void k_dist_empty(gs_distortion_fwd_args a,
   }
 }
 
-// k_feat_bwd's two phases with a per-pixel, per-entry X_i in place of the
+// The group walk with a per-pixel, per-entry X_i in place of the feature
 // payload's dot product, for a cotangent g on the distortion:
 //   X_i = 2 g [m_i (A_{i-1} + A_i - A_n) + S_n - S_i - S_{i-1}]   (= g dD/dc_i),  K = 2 g D
 //   dL/dm_i = 2 g c_i (A_{i-1} + A_i - A_n),  dL/dz_i = dL/dm_i q_i r_i   (1 | kappa / z_i^2)
@@ -779,162 +693,53 @@ __global__ __launch_bounds__(kWave) void k_dist_bwd(gs_distortion_bwd_args a, fl
   __shared__ float s_dm[kBwdGroup][kBwdRow];   // ... and dL/dm
   __shared__ float2 s_wrec[kBwdGroup * 6];     // the group's records: (mx my h00 h11) (ho o z q) (r - slot -)
   Replay r;
-  const int ncell = a.cell_count;
-  if (!replay_setup(r, a.cam, a.tiles_x, a.tiles_y, ncell, a.cell_begin, a.ranges, (uint32_t)a.num_pairs,
-                    a.cell_neval, a.live_bits, a.live_words))
-    return;
-  const int qb = r.quad - a.cell_begin;  // the cell's partial group
+  if (!replay_setup(r, a, a.cell_count, a.cell_begin)) return;
   const int lane = threadIdx.x;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
   // the pixel's cotangent and the forward's state (lanes outside read pixel 0, unused)
   const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
   const size_t p = r.inside ? (size_t)r.py * a.cam.image_width + r.px : 0;
   const float g2 = r.inside ? 2.f * a.g_distortion[p] : 0.f;
   const float An = a.moments[p], Sn = a.moments[HW + p];
-  const float fx = (float)r.px, fy = (float)r.py;
   // PG = P - K as one running sum (k_feat_bwd), K = 2 g D
   float PG = -(g2 * a.distortion[p]);
-  float A = 0.f, S = 0.f, T1 = 1.f, zf = 0.f, rf = 1.f;
-  bool run = r.inside;
-  float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, rz = r0;
-  auto fetch = [&](uint32_t wd, unsigned long long m) {
-    if ((m >> lane) & 1ull) {
-      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
-      r0 = recs[3 * (size_t)gid];
-      r1 = recs[3 * (size_t)gid + 1];
-      r2 = recs[3 * (size_t)gid + 2];
-      rz = dist_payload(r2.y, gid, kappa);
-    }
-  };
-  // Phase B over a group: its k live entries, staged at s_wrec positions 0 .. k - 1.
-  auto phase_b = [&](int k) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group buffer rows this wave wrote
-    const int j = lane / kBwdLanes, col = lane % kBwdLanes;
-    if (j < k) {
-      const uint32_t e = (uint32_t)j;
-      const float4 ia = reinterpret_cast<const float4 *>(s_wrec)[3 * e];  // mx my h00 h11 (h = -q/2)
-      const float4 ib = reinterpret_cast<const float4 *>(s_wrec)[3 * e + 1];  // ho o z q
-      const float q00 = -2.f * ia.z, q11 = -2.f * ia.w, qo = -2.f * ib.x;  // (exact)
-      const float zr = s_wrec[6 * e + 4].x;
-      const uint32_t slot = __float_as_uint(s_wrec[6 * e + 5].x);
-      const float hop = -0.5f * ib.y;
-      // (k_feat_bwd's column walk: the row moments about the column row nearest the mean)
-      const float bx = (float)(r.x0 + col) - ia.x;
-      const float rc = __builtin_amdgcn_fmed3f(__builtin_rintf(ia.y - (float)r.y0), 0.f, (float)(kBwdGroup - 1));
-      float S0 = 0.f, Soy = 0.f, Soyy = 0.f, g5 = 0.f, g9 = 0.f;
-#pragma unroll
-      for (int row = 0; row < kBwdGroup; ++row) {
-        const int pp = col + 8 * row;  // phase A's lane of that pixel
-        const float2 dc = s_dc[j][pp];
-        const float dop = dc.x, cs = dc.y;
-        const float ds = cs > 0.f ? dop : 0.f;
-        const float wr = (float)row - rc;  // exact: small integers
-        S0 += ds;
-        Soy = __builtin_fmaf(ds, wr, Soy);
-        Soyy = __builtin_fmaf(ds, wr * wr, Soyy);
-        g5 += dop;
-        g9 += s_dm[j][pp];
-      }
-      S0 *= hop;
-      Soy *= hop;
-      Soyy *= hop;
-      const float by = (float)r.y0 + rc - ia.y;
-      float Sx = bx * S0, Sy = __builtin_fmaf(by, S0, Soy);
-      float g2s = bx * Sx, g3 = bx * Sy;
-      float g4 = __builtin_fmaf(by, __builtin_fmaf(by, S0, 2.f * Soy), Soyy);
-      Sx = oct_sum(Sx); Sy = oct_sum(Sy); g2s = oct_sum(g2s); g3 = oct_sum(g3); g4 = oct_sum(g4);
-      g5 = oct_sum(g5); g9 = oct_sum(g9);
-      if (col == 0) {
-        const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
-        const size_t sq = (size_t)slot * (uint32_t)ncell + (uint32_t)qb;
-        if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
-          float *out = a.pair_grads + sq * GS_PARTIAL_STRIDE;  // (dense 40-B partials, 8-B aligned: f4_u8)
-          *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2s, g3};
-          *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, 0.f, 0.f};
-          *reinterpret_cast<f2_u8 *>(out + 8) = f2_u8{0.f, kInv ? g9 * (ib.w * zr) : g9};  // dm/dz = q r
-          a.slot_live[sq] = 1;
-        }
-      }
-    }
-  };
-  unsigned long long mcur = r.live_word(0);
-  fetch(0, mcur);
-  for (uint32_t wd = 0; wd < r.nwords; ++wd) {
-    // the entry's gradient slot, as k_feat_bwd forms it
-    const bool mine = (mcur >> lane) & 1ull;
-    const uint32_t info = __float_as_uint(r2.w);
-    const uint32_t slot = __float_as_uint(r2.z) + (r.ty - ((info >> 12) & 0xFFFu)) * ((info >> 24) + 1u) +
-                          (r.tx - (info & 0xFFFu));
-    const uint32_t rank =
-        __builtin_amdgcn_mbcnt_hi((uint32_t)(mcur >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mcur, 0u));
-    const float4 c0 = make_float4(r0.x, r0.y, -0.5f * r0.z, -0.5f * r0.w);
-    const float4 c1 = make_float4(-0.5f * r1.x, r1.y, rz.x, rz.y);
-    const float4 c2 = make_float4(rz.z, 0.f, __uint_as_float(slot), 0.f);
-    const unsigned long long mnext = wd + 1u < r.nwords ? r.live_word(wd + 1u) : 0ull;
-    fetch(wd + 1u, mnext);  // in flight while this word replays
-    unsigned long long m = mcur;
-    uint32_t kb = 0;  // packed position of the group's first entry
-    while (m) {
-      int k = 0;
-      // (the previous group's reads came before these writes in this wave's in-order LDS queue)
-      if (mine && rank - kb < (uint32_t)kBwdGroup) {
-        float4 *d = reinterpret_cast<float4 *>(&s_wrec[6 * (rank - kb)]);
-        d[0] = c0;
-        d[1] = c1;
-        d[2] = c2;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staged records, for every lane
-      const char *cb = reinterpret_cast<const char *>(s_wrec);
-#pragma unroll
-      for (int kk = 0; kk < kBwdGroup; ++kk) {
-        if (kk > 0 && !m) break;
-        m &= m - 1ull;
-        const float4 r0v = reinterpret_cast<const float4 *>(cb + 48 * kk)[0];
-        const float4 r1v = reinterpret_cast<const float4 *>(cb + 48 * kk)[1];
-        const float zr = reinterpret_cast<const float2 *>(cb + 48 * kk)[4].x;
-        const float dx = fx - r0v.x, dy = fy - r0v.y;
-        const float tq = conic_s(dx, dy, r0v.z, r1v.x, r0v.w);  // -s/2, as in the forward
-        const bool live = run && !(tq < kSkipT);
-        const float e = exp_blend(tq);
-        const float w = sat01(e);
-        const float u = r1v.y * w;
-        const float ai = sat01(u);
-        const float trans = T1;
-        const float c = trans * (live ? ai : 0.f);
+  float S = 0.f, zf = 0.f, rf = 1.f;
+  float4 *wrec = reinterpret_cast<float4 *>(s_wrec);
+  group_walk<Rec3>(
+      r, a, wrec,
+      [&](uint32_t gid, const float4 &r2) {
+        const float4 zqr = dist_payload(r2.y, gid, kappa);
+        return make_float4(zqr.x, zqr.y, zqr.z, 0.f);  // (the id is not staged)
+      },
+      [&](int kk, const float4 *rec, const ChainStep &st) {
+        const float4 r1v = rec[1];
+        const float zr = rec[2].x;
+        const float c = st.p.c;
         // the forward's reference and prefix sums, operation for operation
-        const bool have = A > 0.f;
+        const bool have = st.A0 > 0.f;
         zf = have ? zf : r1v.z;
         float md = r1v.z - zf;
         if constexpr (kInv) {
           rf = have ? rf : zr;
           md *= r1v.w * rf;
         }
-        const float Ap = A, Sp = S;
+        const float Sp = S;
         S = __builtin_fmaf(c, md, S);
-        A = A + c;
-        const float u3 = (Ap + A) - An;
+        const float u3 = (st.A0 + st.A1) - An;
         const float X = g2 * __builtin_fmaf(md, u3, (Sn - S) - Sp);
         PG = __builtin_fmaf(c, X, PG);
-        const bool term = !(A < kAlphaStop);
-        T1 = 1.f - A;
-        const float inv = __builtin_amdgcn_rcpf(T1);  // v_rcp_f32 (1 ulp): a gradient factor, no decision
-        const float d_live = __builtin_fmaf(inv, PG, X);
-        // the terminating contributor has nothing behind it
-        const float dal = trans * (term ? X : d_live);
-        run = run && !term;
-        const float g = (ai == u) ? dal * w : 0.f;
-        const float dop = (c > 0.f) ? g : 0.f;
-        const float cw = (w == e) ? c : -c;  // c == +0 when skipped
-        s_dc[kk][lane] = make_float2(dop, cw);
+        s_dc[kk][lane] = step_grad(st, X, PG);
         s_dm[kk][lane] = (g2 * c) * u3;
-        k = kk + 1;
-      }
-      phase_b(k);
-      kb += (uint32_t)k;
-    }
-    mcur = mnext;
-  }
+      },
+      [&](int k) {
+        float g9 = 0.f;
+        phase_b_geometry(
+            r, a, wrec, s_dc, k, [&](int j, int pp, float) { g9 += s_dm[j][pp]; },
+            [&](int j) {
+              const float dm = oct_sum(g9);
+              const float q = wrec[3 * j + 1].w, zr = wrec[3 * j + 2].x;
+              return make_float4(0.f, 0.f, 0.f, kInv ? dm * (q * zr) : dm);  // dm/dz = q r
+            });
+      });
 }
 
 // near == far == 0: the linear map (kappa 0); else 0 < near < far, both finite
@@ -945,15 +750,6 @@ bool near_far_ok(float near, float far) {
 
 float near_far_kappa(float near, float far) {
   return (near == 0.f && far == 0.f) ? 0.f : (float)((double)far * near / ((double)far - near));
-}
-
-int cells_per_tile(int tile_size) {
-  const int qx = (tile_size + GS_QUAD - 1) / GS_QUAD;
-  return qx * qx;
-}
-
-bool tiles_match(const gs_camera &c, int tiles_x, int tiles_y) {
-  return tiles_x == (int)div_up(c.image_width, c.tile_size) && tiles_y == (int)div_up(c.image_height, c.tile_size);
 }
 
 bool channels_ok(int channels) { return channels >= 1 && channels <= GS_MAX_FEATURE_CHANNELS; }
@@ -977,9 +773,9 @@ gs_status gs_blend_features_forward(const gs_feature_fwd_args *a, gs_stream_t st
   if (a->num_pairs < 0 || a->num_gaussians < 1)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
   const long long chunks = div_up(a->channels, GS_FEATURE_CHUNK);
-  const long long blocks = (long long)div_up((long long)a->tiles_x * a->tiles_y, 8) * 8LL * cells_per_tile(a->cam.tile_size);
-  // (a launch's work-items, workgroups x 64, must stay below 2^32)
-  if (blocks * chunks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  long long blocks;
+  if (!cell_grid(a->tiles_x, a->tiles_y, cells_per_tile(a->cam.tile_size), &blocks, chunks))
+    return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
   k_feat_fwd<<<dim3((unsigned)blocks, (unsigned)chunks), kWave, 0, (hipStream_t)stream>>>(*a);
   return gs_internal_check_launch(me);
 }
@@ -999,14 +795,9 @@ gs_status gs_blend_features_backward(const gs_feature_bwd_args *a, gs_stream_t s
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
   if (a->num_pairs < 0 || a->num_gaussians < 1)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
-  const int cells = cells_per_tile(a->cam.tile_size);
   gs_feature_bwd_args b = *a;
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
-                "[0, gs_tile_quads(tile_size))", me);
-  const long long blocks = (long long)div_up((long long)b.tiles_x * b.tiles_y, 8) * 8LL * b.cell_count;
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  long long blocks;
+  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
   k_feat_bwd<<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b);
   return gs_internal_check_launch(me);
 }
@@ -1048,14 +839,9 @@ gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream) {
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
   if (!a->dominant_id != !a->dominant_weight)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: dominant_id and dominant_weight go together", me);
-  const int cells = cells_per_tile(a->cam.tile_size);
   gs_contrib_args b = *a;
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
-                "[0, gs_tile_quads(tile_size))", me);
-  const long long blocks = (long long)div_up((long long)b.tiles_x * b.tiles_y, 8) * 8LL * b.cell_count;
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  long long blocks;
+  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
   if (b.num_gaussians == 0 || b.num_pairs == 0) {
     if (!b.dominant_id) return GS_OK;
     const long long pixels = (long long)b.cam.image_width * b.cam.image_height;
@@ -1079,9 +865,9 @@ gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream
   if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
   if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
-  const long long blocks = (long long)div_up((long long)a->tiles_x * a->tiles_y, 8) * 8LL * cells_per_tile(a->cam.tile_size);
-  // (a launch's work-items, workgroups x 64, must stay below 2^32)
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  long long blocks;
+  if (!cell_grid(a->tiles_x, a->tiles_y, cells_per_tile(a->cam.tile_size), &blocks))
+    return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
   if (a->num_gaussians == 0 || a->num_pairs == 0) {
     const long long pixels = (long long)a->cam.image_width * a->cam.image_height;
     k_dist_empty<<<div_up(pixels, kBlock), kBlock, 0, (hipStream_t)stream>>>(*a, pixels);
@@ -1108,14 +894,9 @@ gs_status gs_blend_distortion_backward(const gs_distortion_bwd_args *a, gs_strea
   if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
   if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
-  const int cells = cells_per_tile(a->cam.tile_size);
   gs_distortion_bwd_args b = *a;
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;  // (0: every cell, one batch)
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
-                "[0, gs_tile_quads(tile_size))", me);
-  const long long blocks = (long long)div_up((long long)b.tiles_x * b.tiles_y, 8) * 8LL * b.cell_count;
-  if (blocks * kWave > 0xffffffffLL) return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
+  long long blocks;
+  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
   const float kappa = near_far_kappa(b.near, b.far);
   if (kappa != 0.f)
     k_dist_bwd<true><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b, kappa);

@@ -314,23 +314,6 @@ __global__ __launch_bounds__(kBlock) void k_project_fwd(gs_project_args a) {
 // to kGatherNB slots are loaded at once, then their partials: two round trips
 // per kGatherNB x HL slots of g (the mean is 4.4 on C3).  Partials are 40 B, 8-B aligned:
 // read as float2.
-__device__ __forceinline__ float quad_sum(float v) {
-  v += dpp_row<0xB1>(v);  // quad_perm [1,0,3,2]
-  v += dpp_row<0x4E>(v);  // quad_perm [2,3,0,1]
-  asm volatile("" : "+v"(v));
-  return v;
-}
-template <int LPG>
-__device__ __forceinline__ float lanes_sum(float v) {
-  if constexpr (LPG == 8) return oct_sum(v);
-  if constexpr (LPG == 4) return quad_sum(v);
-  if constexpr (LPG == 2) {
-    v += dpp_row<0xB1>(v);
-    asm volatile("" : "+v"(v));
-    return v;
-  }
-  return v;
-}
 
 constexpr int kGatherHL1 = 4;  // slot lanes per Gaussian with one partial group per slot
 
