@@ -1353,6 +1353,70 @@ gs_status gs_render_backward(gs_render_bwd_args *a, gs_stream_t stream);
 void gs_frame_offsets(int32_t n, int32_t width, int32_t height, int32_t tile_size, size_t out[14]);
 void gs_tile_offsets(int64_t capacity, int32_t num_tiles, int32_t live_cells, int32_t flag_groups, size_t out[9]);
 
+/* ---- Bilateral grid (Wang et al., "Bilateral Guided Radiance Field
+ * Processing", SIGGRAPH 2024; HDRNet's slicing; gsplat's use_bilateral_grid) ---
+ * Appearance compensation: one small learnable grid of affine colour
+ * transforms per training image, sliced per pixel and applied to the render
+ * before the photometric loss, held smooth by a total-variation term.  It sits
+ * wholly behind the rendered image.  Stream ordered, no allocation, no atomics,
+ * no host sync, the same bits every run; every check below returns
+ * GS_ERR_INVALID_ARG before any HIP call.
+ *
+ * A grid G is [12, L, Gh, Gw] fp32, channel 4c + k entry (c, k) of a 3x4 affine
+ * matrix; 2 <= L <= GS_BILAGRID_MAX_L, 2 <= Gh, Gw <= GS_BILAGRID_MAX_XY.  For
+ * pixel (x, y) of the [3, H, W] image rgb = (r, g, b), in fp32:
+ *   u = (x + 0.5) / W * (Gw - 1),  v = (y + 0.5) / H * (Gh - 1)
+ *   gray = (0.299 r + 0.587 g) + 0.114 b,  z = clamp(gray, 0, 1) * (L - 1)
+ *   along each axis  i0 = clamp(floor(t), 0, n - 2),  f = t - i0
+ *   A = trilinear(G; u, v, z) as nested lerps a0 + f (a1 - a0): x, then y, then z
+ *   out[c] = ((A[c,0] r + A[c,1] g) + A[c,2] b) + A[c,3]
+ * (torch's 5-D grid_sample, bilinear, border padding, align_corners; a grid
+ * constant over its nodes is sliced exactly, the identity grid returns the
+ * image bit for bit).  The backward stores, from g_out [3, H, W],
+ *   d_grid[4c+k, node] = sum over the pixels of  w_x w_y w_z  g_out[c] (r, g, b, 1)[k]
+ *     with each axis' weights 1 - f at i0 and f at i0 + 1 -- every node is
+ *     written, a node no pixel touches gets an exact 0 -- and
+ *   d_rgb[k] = sum_c g_out[c] A[c,k]
+ *              + coef[k] (L - 1) [0 < gray < 1] sum_c g_out[c] (dA/dz)[c,:] . (r, g, b, 1)
+ *     with coef = (0.299, 0.587, 0.114) and dA/dz = a1 - a0 of the z lerp (no
+ *     gradient through the guidance where gray is clamped; u, v are constants).
+ * The forward is one launch of one thread per pixel; the backward two: d_rgb
+ * per pixel, and d_grid as a gather -- one workgroup per node column (gx, gy)
+ * walks the pixels of the column's two-cell footprint, every thread keeps the
+ * column's L x 12 sums in registers, and the workgroup adds them in a fixed
+ * order.  The per-pixel kernels keep the grid in LDS when it fits 112 KiB (the
+ * default shape takes 96) and read it from memory otherwise.  width, height
+ * >= 1 (height <= 262140, at most 2^30 tiles of 64 x 16 pixels). */
+#define GS_BILAGRID_CHANNELS 12
+#define GS_BILAGRID_MAX_L 16
+#define GS_BILAGRID_MAX_XY 64
+typedef struct gs_bilagrid_slice_args {
+  int32_t width, height;          /* the image */
+  int32_t grid_w, grid_h, grid_l; /* Gw, Gh, L */
+  const float *grid;              /* [12, L, Gh, Gw] */
+  const float *rgb;               /* [3,H,W] */
+  float *out;                     /* [3,H,W] (forward) */
+  const float *g_out;             /* [3,H,W] (backward) */
+  float *d_rgb;                   /* [3,H,W] (backward) */
+  float *d_grid;                  /* [12, L, Gh, Gw] (backward) */
+} gs_bilagrid_slice_args;
+gs_status gs_bilagrid_slice_forward(const gs_bilagrid_slice_args *a, gs_stream_t stream);
+gs_status gs_bilagrid_slice_backward(const gs_bilagrid_slice_args *a, gs_stream_t stream);
+
+/* gs_bilagrid_tv: the total variation of one grid and its gradient, one launch
+ * of one workgroup (the sums in double, in a fixed order):
+ *   tv = mean_x-pairs (G[.., x+1] - G[.., x])^2 + mean_y-pairs (..)^2 + mean_z-pairs (..)^2
+ * each mean over that axis' own neighbour pairs and all 12 channels, and
+ *   d_grid[n] = sum over the axes of (2 / pairs_axis) ((G[n] - G[n - 1]) - (G[n + 1] - G[n]))
+ * (a difference that has no neighbour is 0).  tv is one float. */
+typedef struct gs_bilagrid_tv_args {
+  int32_t grid_w, grid_h, grid_l;
+  const float *grid; /* [12, L, Gh, Gw] */
+  float *tv;         /* [1] */
+  float *d_grid;     /* [12, L, Gh, Gw]: d tv / d grid */
+} gs_bilagrid_tv_args;
+gs_status gs_bilagrid_tv(const gs_bilagrid_tv_args *a, gs_stream_t stream);
+
 /* ---- misc --------------------------------------------------------------- */
 int32_t gs_abi_version(void);
 const char *gs_last_error(void);

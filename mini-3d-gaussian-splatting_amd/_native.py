@@ -370,6 +370,20 @@ class GsNormalConsistencyArgs(C.Structure):
                 ("error", _vp), ("surface_normals", _vp), ("g_error", _vp), ("d_normals", _vp), ("d_depth", _vp)]
 
 
+GS_BILAGRID_CHANNELS, GS_BILAGRID_MAX_L, GS_BILAGRID_MAX_XY = 12, 16, 64  # a grid is [12, L, Gh, Gw]
+
+
+class GsBilagridSliceArgs(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("grid_w", C.c_int32), ("grid_h", C.c_int32),
+                ("grid_l", C.c_int32), ("grid", _vp), ("rgb", _vp), ("out", _vp), ("g_out", _vp), ("d_rgb", _vp),
+                ("d_grid", _vp)]
+
+
+class GsBilagridTvArgs(C.Structure):
+    _fields_ = [("grid_w", C.c_int32), ("grid_h", C.c_int32), ("grid_l", C.c_int32), ("grid", _vp), ("tv", _vp),
+                ("d_grid", _vp)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -388,6 +402,7 @@ EXPORTS = (
     "gs_adam_step_rows",
     "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
     "gs_normal_consistency_forward", "gs_normal_consistency_backward",
+    "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv",
 )
 
 _lib = None
@@ -473,6 +488,9 @@ def _declare(lib):
     lib.gs_gaussian_normals_backward.argtypes = [P(GsGaussianNormalsArgs), _vp]
     lib.gs_normal_consistency_forward.argtypes = [P(GsNormalConsistencyArgs), _vp]
     lib.gs_normal_consistency_backward.argtypes = [P(GsNormalConsistencyArgs), _vp]
+    lib.gs_bilagrid_slice_forward.argtypes = [P(GsBilagridSliceArgs), _vp]
+    lib.gs_bilagrid_slice_backward.argtypes = [P(GsBilagridSliceArgs), _vp]
+    lib.gs_bilagrid_tv.argtypes = [P(GsBilagridTvArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
@@ -482,7 +500,8 @@ def _declare(lib):
               "gs_mcmc_regularize", "gs_blend_backward_abs", "gs_gather_abs_partials",
               "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
               "gs_adam_step_rows", "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
-              "gs_normal_consistency_forward", "gs_normal_consistency_backward"):
+              "gs_normal_consistency_forward", "gs_normal_consistency_backward",
+              "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -117,6 +117,17 @@ class TrainingConfig:
     # every other row keeps its parameters and both Adam moments bit for bit instead of drifting along a
     # stale first moment.  Step counts stay per tensor.  Not for the replayed step (GraphedStep)
     visible_adam: bool = False
+    # bilateral-grid appearance compensation (Wang et al. 2024; gsplat's use_bilateral_grid; bilagrid.py): every
+    # training image gets a learnable (Gw, Gh, L) grid of affine colour transforms -- bilateral_grid_shape --
+    # that is sliced per pixel and applied to the training render before the photometric loss, absorbing the
+    # frame's exposure and white balance; the loss gains lambda_tv * the grid's total variation.  The grids have
+    # their own Adam: bilateral_grid_lr * min(1, 0.01 + 0.99 it / bilateral_grid_warmup) * 0.01^(it / iterations).
+    # Evaluation renders stay uncorrected.  False: no new launch, the step's bits are the ones they were
+    bilateral_grid: bool = False
+    bilateral_grid_shape: tuple = (16, 16, 8)
+    bilateral_grid_lr: float = 2e-3
+    bilateral_grid_warmup: int = 1000
+    lambda_tv: float = 10.0
 
     def __post_init__(self):
         # (a YAML file holds the iterations as a list)
@@ -124,6 +135,8 @@ class TrainingConfig:
             self.contribution_prune_iterations = tuple(self.contribution_prune_iterations)
         if isinstance(self.distortion_near_far, list):
             self.distortion_near_far = tuple(self.distortion_near_far)
+        if isinstance(self.bilateral_grid_shape, list):
+            self.bilateral_grid_shape = tuple(self.bilateral_grid_shape)
 
     def check(self) -> None:
         """Values no run can use (the trainer asks at setup)."""
@@ -162,6 +175,22 @@ class TrainingConfig:
         it = self.normal_from_iter
         if isinstance(it, bool) or not isinstance(it, int) or it < 0:
             raise ValueError(f"normal_from_iter must be an integer >= 0, got {it!r}")
+        if not isinstance(self.bilateral_grid, bool):
+            raise ValueError(f"bilateral_grid must be a bool, got {self.bilateral_grid!r}")
+        gs = self.bilateral_grid_shape
+        if not (isinstance(gs, tuple) and len(gs) == 3 and all(isinstance(v, int) and not isinstance(v, bool) for v in gs)
+                and 2 <= gs[0] <= 64 and 2 <= gs[1] <= 64 and 2 <= gs[2] <= 16):
+            raise ValueError("bilateral_grid_shape must be (Gw, Gh, L) integers with 2 <= Gw, Gh <= 64 and 2 <= L <= 16, "
+                             f"got {gs!r}")
+        lr = float(self.bilateral_grid_lr)
+        if not (lr > 0.0 and lr != float("inf")):
+            raise ValueError(f"bilateral_grid_lr must be finite and > 0, got {self.bilateral_grid_lr!r}")
+        it = self.bilateral_grid_warmup
+        if isinstance(it, bool) or not isinstance(it, int) or it < 0:
+            raise ValueError(f"bilateral_grid_warmup must be an integer >= 0, got {it!r}")
+        lam = float(self.lambda_tv)
+        if not (lam >= 0.0 and lam != float("inf")):
+            raise ValueError(f"lambda_tv must be finite and >= 0, got {self.lambda_tv!r}")
         nf = self.distortion_near_far
         if nf is not None:
             ok = isinstance(nf, (tuple, list)) and len(nf) == 2 and all(isinstance(v, (int, float)) for v in nf)

@@ -21,11 +21,16 @@ depth distortion of the view (render(depth_distortion=True)), and with lambda_no
 iteration normal_from_iter, lambda_normal times the mean normal consistency error of the view
 (render(normals=True), normals.normal_consistency; no state between steps).  With visible_adam the Adam step
 updates only the Gaussians the step's view saw (the render's visibility_filter); every other row
-keeps its parameters and both moments bit for bit.  Nothing in a step reads a value
+keeps its parameters and both moments bit for bit.  With bilateral_grid every training camera has a
+bilateral grid of affine colour transforms (bilagrid.BilateralGrids, indexed by the camera's position in
+get_train_cameras()): the step's render is sliced through its camera's grid before the photometric loss, the
+loss gains lambda_tv times that grid's total variation, and the grid takes its own Adam step right after the
+backward; only that grid and its moments change.  Nothing in a step reads a value
 back to the host; losses are logged every log_interval iterations.  A
 checkpoint holds what a later step reads -- parameters, Adam moments and step
 counts, the 3D filter, the "screen" statistics accumulated since the last
-densification -- so a resumed run is the uninterrupted one, bit for bit.
+densification, the bilateral grids with their moments and step counts -- so
+a resumed run is the uninterrupted one, bit for bit.
 
 Data parallel: with torch.distributed initialised,
 rank r renders camera perm[(i * world + r) mod n] at iteration i; every rank
@@ -34,7 +39,12 @@ gradients are identical after the all-reduce and the clone jitter is seeded
 by the iteration), so the replicas stay bit-identical.  With visible_adam the
 step's mask is the union of the ranks' visibility (one MAX all-reduce of the N
 mask bytes, issued after the render and before the backward's gradient
-ranges): the averaged gradient is non-zero for the rows any rank saw.
+ranges): the averaged gradient is non-zero for the rows any rank saw.  With
+bilateral_grid each rank divides its grid's gradient by the world size, the
+ranks all-gather (image index, gradient), and every rank applies all of them
+in rank order -- summed first, in rank order, where two ranks drew the same
+image -- in one Adam step (the gathered image indices are the one value such a
+step reads back to the host).
 """
 from __future__ import annotations
 
@@ -47,6 +57,7 @@ import torch
 
 from .config import TrainingConfig
 from .dataset import CameraDataset, load_dataset
+from . import bilagrid as _bilagrid
 from .filter3d import Filter3D
 from .gaussian_model import GaussianModel
 from .loss import photometric_loss
@@ -73,6 +84,9 @@ class GaussianTrainer:
         self.last_densify: Optional[dict] = None  # the counts of the latest densification
         self.last_compact: Optional[dict] = None  # the counts of the latest contribution pruning
         self.filter_3d: Optional[Filter3D] = None  # config.filter_3d: the 3D smoothing filter of every render
+        # config.bilateral_grid: one grid per training camera, and where each camera stands in that list
+        self.bilagrid: Optional[_bilagrid.BilateralGrids] = None
+        self._grid_index: Dict[int, int] = {}
 
     # -- setup (trainer.py:32-44) ------------------------------------------
     def _device(self) -> torch.device:
@@ -111,6 +125,43 @@ class GaussianTrainer:
         self.optimizer = GaussianOptimizer(g, c)
         self.optimizer.setup_optimizer()
         self._update_filter_3d()
+        self._setup_bilagrid()
+
+    def _setup_bilagrid(self) -> None:
+        """config.bilateral_grid: identity grids, one per training camera."""
+        c = self.config
+        if not c.bilateral_grid:
+            return
+        cams = self.dataset.get_train_cameras()
+        self.bilagrid = _bilagrid.BilateralGrids(len(cams), self._device(), c.bilateral_grid_shape,
+                                                 lr=c.bilateral_grid_lr)
+        self._grid_index = {id(cam): i for i, cam in enumerate(cams)}
+
+    def _bilagrid_lr(self, it: int) -> float:
+        c = self.config
+        ramp = 1.0 if c.bilateral_grid_warmup <= 0 else min(1.0, 0.01 + 0.99 * it / c.bilateral_grid_warmup)
+        return c.bilateral_grid_lr * ramp * 0.01 ** (it / max(c.iterations, 1))
+
+    def _bilagrid_step(self, index: int) -> None:
+        """The step's grid update, right after the backward.  Data parallel:
+        every rank's (image index, gradient / world) is gathered through the
+        process group and applied by every rank, in rank order."""
+        bg = self.bilagrid
+        bg.set_lr(self._bilagrid_lr(self.iteration))
+        if self._dist is not None:
+            world = self._dist.get_world_size()
+            grad = bg.grids[index].grad / world
+            dev = grad.device
+            idx = torch.tensor([index], dtype=torch.int64, device=dev)
+            all_idx = [torch.empty_like(idx) for _ in range(world)]
+            all_grad = [torch.empty_like(grad) for _ in range(world)]
+            self._dist.all_gather(all_idx, idx)
+            self._dist.all_gather(all_grad, grad.contiguous())
+            grads: Dict[int, torch.Tensor] = {}
+            for i, g in zip(torch.cat(all_idx).tolist(), all_grad):
+                grads[i] = grads[i] + g if i in grads else g
+            bg.set_grads(grads)
+        bg.step()
 
     def _update_filter_3d(self) -> None:
         """config.filter_3d: the filter of the current rows from all training
@@ -152,6 +203,13 @@ class GaussianTrainer:
         if c.filter_3d and self.iteration % c.filter_3d_interval == 0:
             self._update_filter_3d()
         opt.zero_grad()
+        grid = None
+        if self.bilagrid is not None:
+            grid = self._grid_index.get(id(camera))
+            if grid is None:
+                raise ValueError("bilateral_grid: train_step needs one of the dataset's training cameras (each has "
+                                 "its own grid)")
+            self.bilagrid.zero_grad()
         if self._dist is not None:
             # the bucket is attached before the render, so that its backward
             # writes the gradients into it and reduces them range by range
@@ -178,13 +236,18 @@ class GaussianTrainer:
         out = self.renderer.render(camera, g, self._settings(camera), **extra)
         visible = self._visible_mask(out) if c.visible_adam else None
         target = camera._image
-        total, l1, dssim = photometric_loss(out["image"], target, self.config.lambda_dssim)
+        image = out["image"] if grid is None else self.bilagrid.slice(grid, out["image"])
+        total, l1, dssim = photometric_loss(image, target, self.config.lambda_dssim)
+        if grid is not None and c.lambda_tv > 0:
+            total = total + c.lambda_tv * self.bilagrid.tv(grid)
         if distort:
             total = total + c.lambda_distortion * out["distortion"].mean()
         if normal:
             total = total + c.lambda_normal * _normals.normal_consistency(out["normals"], out["depth"], out["alpha"],
                                                                           camera).mean()
         total.backward()
+        if grid is not None:
+            self._bilagrid_step(grid)
         opt.update_learning_rate(self.iteration)
         if c.densify_criterion == "mcmc":
             self._mcmc_update(visible)
@@ -303,7 +366,10 @@ class GaussianTrainer:
 
     @torch.no_grad()
     def validate(self) -> Dict[str, float]:
-        """trainer.py:71-75: mean PSNR and loss over the test cameras (train if none)."""
+        """trainer.py:71-75: mean PSNR and loss over the test cameras (train if
+        none).  The renders are not corrected by config.bilateral_grid's grids:
+        a test camera has none, so the metrics are those of the raw render
+        (colour-corrected evaluation is not implemented)."""
         cams = self.dataset.get_test_cameras() or self.dataset.get_train_cameras()
         psnr, loss = [], []
         for cam in cams:
@@ -338,6 +404,9 @@ class GaussianTrainer:
         if self._density_stats_in_checkpoint():
             for name, v in self._density_state().items():
                 tensors[f"density.{name}"] = v.contiguous()
+        if self.bilagrid is not None:
+            for name, v in self.bilagrid.state().items():
+                tensors[f"bilagrid.{name}"] = v.contiguous()
         meta = {"iteration": str(iteration), "active_sh_degree": str(self.gaussians.active_sh_degree)}
         if self.last_densify is not None:
             meta["last_densify"] = json.dumps(self.last_densify)
@@ -412,6 +481,11 @@ class GaussianTrainer:
             else:  # (a checkpoint of a run without the filter)
                 self.filter_3d = None
                 self._update_filter_3d()
+        if self.config.bilateral_grid:
+            self._setup_bilagrid()  # identity grids: what a checkpoint of a run without the option resumes from
+            if "bilagrid.grids" in t:
+                self.bilagrid.load_state({k: t[f"bilagrid.{k}"].to(dev) if k != "step" else t[f"bilagrid.{k}"]
+                                          for k in ("grids", "m", "v", "step")})
 
 
 __all__ = ["GaussianTrainer", "TrainingConfig"]
