@@ -1417,6 +1417,100 @@ typedef struct gs_bilagrid_tv_args {
 } gs_bilagrid_tv_args;
 gs_status gs_bilagrid_tv(const gs_bilagrid_tv_args *a, gs_stream_t stream);
 
+/* ---- TSDF fusion and mesh extraction (KinectFusion's / Open3D's z-projective
+ * running mean, which 2DGS's mesh extraction uses; surface nets, Gibson 1998) --
+ * Rendered depth maps are fused into a truncated signed distance volume and a
+ * triangle mesh is extracted from it.  Stand-alone: nothing here is part of a
+ * render or a training step.  Stream ordered, no allocation, no atomics, no
+ * host sync, the same bits every run; every check below returns before any HIP
+ * call: GS_ERR_INVALID_ARG for a null pointer, a dimension below 1 or a bad
+ * scalar, GS_ERR_UNSUPPORTED for a volume of 2^31 nodes or more.
+ *
+ * A volume is nx x ny x nz samples at the nodes p_ijk = origin + h (i, j, k),
+ * stored [nz, ny, nx] with x fastest: tsdf (initially 1), weight (initially 0)
+ * and optionally color [3, nz, ny, nx] (initially 0), all fp32. */
+typedef struct gs_tsdf_volume {
+  int32_t nx, ny, nz;
+  float origin[3];
+  float voxel_size; /* h, finite and > 0 */
+  float *tsdf;      /* [nz,ny,nx] */
+  float *weight;    /* [nz,ny,nx] */
+  float *color;     /* [3,nz,ny,nx], or NULL */
+} gs_tsdf_volume;
+
+/* gs_tsdf_integrate fuses num_views >= 1 views of one size in one launch.  A
+ * camera row is {view[12], fx, fy, cx, cy}: gs_camera's values, the first 16
+ * floats of a gs_filter3d_rate_args row.  One thread owns a node and visits
+ * the views in table order, in fp32:
+ *   (X, Y, Z) = R p + t, each ((r0 x + r1 y) + r2 z) + t;  skip unless Z > near
+ *   px = (fx X) / Z + cx,  py = (-fy Y) / Z + cy     (the projection's convention)
+ *   u = floor(px + 0.5), v = floor(py + 0.5);  skip outside [0, W) x [0, H)
+ *   d = depth[v, u];  skip unless d > 0 (a NaN skips), if d > depth_max, and
+ *   if alpha is given and alpha[v, u] < alpha_min
+ *   s = d - Z;  skip if s < -trunc;  tau = min(1, s / trunc)
+ *   w' = w + 1;  tsdf = (tsdf w + tau) / w';  color_c = (color_c w + image[c, v, u]) / w'
+ *   (the colour with both a colour volume and an image);  w = w'
+ * The node stays in registers over the views: num_views views in one launch
+ * give the bits of num_views launches of one view each, in order, with one
+ * read and one write of the volume.  A node no view updates is neither read
+ * nor stored to.  near and trunc finite and > 0; alpha_min and depth_max not
+ * NaN (depth_max may be +inf). */
+#define GS_TSDF_CAMERA_FLOATS 16
+typedef struct gs_tsdf_integrate_args {
+  gs_tsdf_volume vol;
+  int32_t num_views, width, height;
+  const float *cameras; /* [V, GS_TSDF_CAMERA_FLOATS], on the device */
+  const float *depth;   /* [V,H,W] */
+  const float *alpha;   /* [V,H,W], or NULL */
+  const float *image;   /* [V,3,H,W], or NULL */
+  float near, trunc, alpha_min, depth_max;
+} gs_tsdf_integrate_args;
+gs_status gs_tsdf_integrate(const gs_tsdf_integrate_args *a, gs_stream_t stream);
+
+/* Surface nets.  Cell (i, j, k), 0 <= i < nx - 1 and likewise j, k, has the 8
+ * nodes (i..i+1, j..j+1, k..k+1) as corners.  A node is inside iff tsdf < 0; a
+ * cell is valid iff all 8 corners have weight >= min_weight, and active iff it
+ * is valid and its corners are not all on one side.  Every such test reads the
+ * stored fp32 values.
+ *
+ * gs_mesh_classify writes, per cell, cell_active (0 / 1), and per node the
+ * number of triangles its three edges emit (node_tris: 0, 2, 4 or 6) and their
+ * 3-bit mask (node_mask, bit a for the edge n -> n + e_a).  With (a, b, c)
+ * cyclic -- x: (y, z), y: (z, x), z: (x, y) -- edge a of node n emits iff its
+ * ends differ in side and the four cells around it, c00 = n - e_b - e_c,
+ * c10 = n - e_c, c11 = n and c01 = n - e_b, all exist and are valid.  One
+ * workgroup classifies a 32 x 8 x 4 tile of nodes from an LDS image of the
+ * tile's side and validity bits with a one-node apron.
+ *
+ * The caller forms the inclusive prefix sums of cell_active and node_tris
+ * (int32) and reads the two totals; gs_mesh_emit then writes
+ *   vertices[r] of the active cell of rank r (linear cell order, i fastest):
+ *     over the cell's 12 edges -- the four x edges, then y, then z, within a
+ *     group by the other two offsets in lexicographic order -- each edge whose
+ *     ends a, b differ in side crosses at q = a + f (b - a), f = f_a / (f_a - f_b),
+ *     in node units relative to the cell; the vertex is
+ *     origin + h ((i, j, k) + mean q), its colour the mean of c_a + f (c_b - c_a);
+ *   faces: per node in linear order, per set mask bit in the order x, y, z, the
+ *     triangles (c00, c10, c11), (c00, c11, c01) of the cells' ranks when n is
+ *     inside -- the normal along +a, from inside to outside -- and with the
+ *     last two indices of each swapped when n is outside.
+ * num_vertices or num_faces 0: that array is not written. */
+typedef struct gs_mesh_args {
+  gs_tsdf_volume vol;         /* read only here */
+  float min_weight;           /* classify; not NaN */
+  uint8_t *cell_active;       /* [nz-1,ny-1,nx-1] (may be NULL when there is no cell) */
+  uint8_t *node_tris;         /* [nz,ny,nx] */
+  uint8_t *node_mask;         /* [nz,ny,nx] */
+  const int32_t *cell_rank;   /* emit: inclusive prefix sum of cell_active */
+  const int32_t *node_faces;  /* emit: inclusive prefix sum of node_tris */
+  int32_t num_vertices, num_faces; /* emit: the two totals */
+  float *vertices;            /* emit: [num_vertices, 3] */
+  float *colors;              /* emit: [num_vertices, 3], or NULL; needs vol.color */
+  int32_t *faces;             /* emit: [num_faces, 3] */
+} gs_mesh_args;
+gs_status gs_mesh_classify(const gs_mesh_args *a, gs_stream_t stream);
+gs_status gs_mesh_emit(const gs_mesh_args *a, gs_stream_t stream);
+
 /* ---- misc --------------------------------------------------------------- */
 int32_t gs_abi_version(void);
 const char *gs_last_error(void);

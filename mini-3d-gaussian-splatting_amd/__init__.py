@@ -12,6 +12,7 @@ from .rasterizer import CameraParams, ContributionStats, DensityStats, rasterize
 from .filter3d import Filter3D, apply_filter_3d  # noqa: F401
 from .normals import gaussian_normals, normal_consistency  # noqa: F401
 from .bilagrid import BilateralGrids, bilateral_grid_tv, slice_bilateral_grid  # noqa: F401
+from .tsdf import TSDFVolume, save_mesh_ply  # noqa: F401
 from .loss import SSIMLoss, GaussianLoss, photometric_loss  # noqa: F401
 from .config import TrainingConfig, ConfigManager  # noqa: F401
 from .dataset import CameraDataset, NeRFSyntheticDataset, COLMAPDataset, load_dataset  # noqa: F401
@@ -19,7 +20,7 @@ from .trainer import GaussianTrainer  # noqa: F401
 from .graph_step import GraphedStep  # noqa: F401
 from .pose import CameraPose, se3_exp  # noqa: F401
 from .mcmc import mcmc_sample, mcmc_relocate, mcmc_noise, mcmc_regularize  # noqa: F401
-from . import _native, synthetic, distributed, optim, loss, dataset, trainer, graph_step, pose, mcmc, filter3d, normals, bilagrid  # noqa: F401
+from . import _native, synthetic, distributed, optim, loss, dataset, trainer, graph_step, pose, mcmc, filter3d, normals, bilagrid, tsdf  # noqa: F401
 
 __all__ = ["GaussianRenderer", "RenderSettings", "GaussianModel", "Camera", "CameraUtils",
            "CameraParams", "rasterize", "camera_params", "SSIMLoss", "GaussianLoss", "photometric_loss",
@@ -27,4 +28,4 @@ __all__ = ["GaussianRenderer", "RenderSettings", "GaussianModel", "Camera", "Cam
            "load_dataset", "GaussianTrainer", "GraphedStep", "CameraPose", "se3_exp", "DensityStats",
            "ContributionStats", "mcmc_sample", "mcmc_relocate", "mcmc_noise", "mcmc_regularize",
            "Filter3D", "apply_filter_3d", "gaussian_normals", "normal_consistency",
-           "BilateralGrids", "bilateral_grid_tv", "slice_bilateral_grid"]
+           "BilateralGrids", "bilateral_grid_tv", "slice_bilateral_grid", "TSDFVolume", "save_mesh_ply"]

@@ -384,6 +384,26 @@ class GsBilagridTvArgs(C.Structure):
                 ("d_grid", _vp)]
 
 
+GS_TSDF_CAMERA_FLOATS = 16  # {view[12], fx, fy, cx, cy} per camera row of gs_tsdf_integrate
+
+
+class GsTsdfVolume(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3),
+                ("voxel_size", C.c_float), ("tsdf", _vp), ("weight", _vp), ("color", _vp)]
+
+
+class GsTsdfIntegrateArgs(C.Structure):
+    _fields_ = [("vol", GsTsdfVolume), ("num_views", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("cameras", _vp), ("depth", _vp), ("alpha", _vp), ("image", _vp), ("near", C.c_float),
+                ("trunc", C.c_float), ("alpha_min", C.c_float), ("depth_max", C.c_float)]
+
+
+class GsMeshArgs(C.Structure):
+    _fields_ = [("vol", GsTsdfVolume), ("min_weight", C.c_float), ("cell_active", _vp), ("node_tris", _vp),
+                ("node_mask", _vp), ("cell_rank", _vp), ("node_faces", _vp), ("num_vertices", C.c_int32),
+                ("num_faces", C.c_int32), ("vertices", _vp), ("colors", _vp), ("faces", _vp)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -403,6 +423,7 @@ EXPORTS = (
     "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
     "gs_normal_consistency_forward", "gs_normal_consistency_backward",
     "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv",
+    "gs_tsdf_integrate", "gs_mesh_classify", "gs_mesh_emit",
 )
 
 _lib = None
@@ -491,6 +512,9 @@ def _declare(lib):
     lib.gs_bilagrid_slice_forward.argtypes = [P(GsBilagridSliceArgs), _vp]
     lib.gs_bilagrid_slice_backward.argtypes = [P(GsBilagridSliceArgs), _vp]
     lib.gs_bilagrid_tv.argtypes = [P(GsBilagridTvArgs), _vp]
+    lib.gs_tsdf_integrate.argtypes = [P(GsTsdfIntegrateArgs), _vp]
+    lib.gs_mesh_classify.argtypes = [P(GsMeshArgs), _vp]
+    lib.gs_mesh_emit.argtypes = [P(GsMeshArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
@@ -501,7 +525,8 @@ def _declare(lib):
               "gs_density_accumulate_abs", "gs_filter3d_accumulate", "gs_filter3d_forward", "gs_filter3d_backward",
               "gs_adam_step_rows", "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
               "gs_normal_consistency_forward", "gs_normal_consistency_backward",
-              "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv"):
+              "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv",
+              "gs_tsdf_integrate", "gs_mesh_classify", "gs_mesh_emit"):
         getattr(lib, f).restype = C.c_int
 
 

@@ -64,6 +64,7 @@ from .loss import photometric_loss
 from . import normals as _normals
 from .optim import GaussianOptimizer
 from .renderer import GaussianRenderer, RenderSettings
+from .tsdf import TSDFVolume, save_mesh_ply
 
 
 class GaussianTrainer:
@@ -340,6 +341,41 @@ class GaussianTrainer:
         g.contribution_stats.reset()
         self._update_filter_3d()
         return info
+
+    @torch.no_grad()
+    def extract_mesh(self, voxel_size: Optional[float] = None, bounds=None, depth: str = "median", cameras=None,
+                     min_weight: float = 1.0, path: Optional[str] = None) -> Dict[str, Optional[torch.Tensor]]:
+        """A triangle mesh of the model: render `cameras` (default: the training
+        cameras) with the training render settings -- the screen filter and
+        the 3D filter -- fuse their depth maps ("median" or "expected",
+        tsdf.TSDFVolume.integrate_renders) into a TSDF volume over `bounds` =
+        (lo, hi) (default: the bounding box of the model's positions, one host
+        read) with `voxel_size` (default: that box's longest edge / 256), and
+        extract the surface.  Returns {"vertices", "faces", "colors"}; with
+        `path` the mesh is also written there as a binary PLY.  Every rank
+        fuses all the cameras (data-parallel fusion is not implemented); no
+        training state changes."""
+        g = self.gaussians
+        if bounds is None:
+            xyz = g._xyz.detach().reshape(-1, 3)
+            if xyz.shape[0] == 0:
+                raise ValueError("extract_mesh needs bounds for a model without Gaussians")
+            lo, hi = xyz.min(0).values.tolist(), xyz.max(0).values.tolist()
+        else:
+            ok = isinstance(bounds, (tuple, list)) and len(bounds) == 2 and \
+                all(isinstance(b, (tuple, list)) and len(b) == 3 for b in bounds)
+            if not ok:
+                raise ValueError(f"bounds must be (lo, hi), each of three numbers, got {bounds!r}")
+            lo, hi = bounds
+        if voxel_size is None:
+            voxel_size = max(float(b) - float(a) for a, b in zip(lo, hi)) / 256.0
+        cams = list(self.dataset.get_train_cameras() if cameras is None else cameras)
+        vol = TSDFVolume.from_bounds(lo, hi, voxel_size, g._xyz.device)
+        vol.integrate_renders(self.renderer, g, cams, self._settings, depth=depth, **self._render_extra())
+        mesh = vol.extract_mesh(min_weight)
+        if path is not None:
+            save_mesh_ply(path, mesh["vertices"], mesh["faces"], mesh["colors"])
+        return mesh
 
     def close(self) -> None:
         """Tear down the data-parallel transport: the native RCCL communicators
