@@ -416,17 +416,44 @@ int64_t gs_blend_backward_groups(int32_t tiles_x, int32_t tiles_y, int32_t cell_
 gs_status gs_blend_backward_lane_stats(const gs_blend_bwd_args *a, uint64_t *hist, uint32_t *per_group,
                                        gs_stream_t stream);
 
+/* ---- The colour forward's saved state, as every replay reads it ------------
+ * The passes below (feature channels, contribution statistics, depth
+ * distortion) evaluate no transmittance chain of their own: they replay the
+ * decisions of the gs_blend_forward that wrote ranges / sorted_gauss /
+ * records / cell_neval / live_bits, bit for bit, as gs_blend_backward does --
+ * one 64-lane workgroup per (tile, 8x8 cell), any tile_size; live_bits NULL:
+ * every entry of a cell's evaluated prefix.  gs_replay_frame is that state;
+ * it is the first member `f` of each pass's argument struct.  Every entry
+ * point checks it the same way, before any HIP call: the camera
+ * (GS_ERR_UNSUPPORTED), tiles_x / tiles_y against the image, a NULL ranges,
+ * records or cell_neval, live_bits without live_words, a negative count
+ * (GS_ERR_INVALID_ARG); a backward needs sorted_gauss and num_gaussians >= 1
+ * always, a forward-type pass needs sorted_gauss only when num_pairs > 0.
+ * (Source-level only: the nested struct occupies exactly the bytes the eleven
+ * fields took when each struct spelled them out -- gs_camera is 108 bytes, the
+ * frame ends at byte 176, 8-aligned -- so every later field keeps its offset
+ * and GS_ABI_VERSION stays.) */
+typedef struct gs_replay_frame {
+  gs_camera cam;                /* the colour forward's (bg is not read) */
+  int32_t tiles_x, tiles_y;
+  const uint32_t *ranges;       /* as gs_blend_fwd_args, after that forward */
+  const uint32_t *sorted_gauss;
+  const float *records;         /* with pair offsets (gs_bin_emit) */
+  const uint32_t *cell_neval;   /* gs_blend_fwd_args.cell_neval, as written */
+  const uint64_t *live_bits;    /* gs_blend_fwd_args.live_bits, as written, or NULL */
+  int64_t live_words;
+  int32_t num_pairs;            /* T */
+  int32_t num_gaussians;        /* n: the rows of a staged feature chunk */
+} gs_replay_frame;
+
 /* ---- Per-Gaussian feature channels through the blend ----------------------
  * features_out[k, p] = sum_i c_i F[g_i, k] over the entries i of pixel p's
  * tile list that the colour forward accepted, with the colour forward's own
  * contribution weights c_i (renderer.py:319-353: w = clamp(exp(-s/2), 0, 1),
  * skipped below 1e-5; alpha = clamp(o w, 0, 1); c = (1 - A) alpha; A += c,
  * break once A >= 0.995).  No background, clamp, sigmoid or normalisation: a
- * pixel no entry reaches gets 0.  The kernels evaluate no transmittance chain
- * of their own: they replay the decisions of the gs_blend_forward that wrote
- * ranges / sorted_gauss / records / cell_neval / live_bits, bit for bit, as
- * gs_blend_backward does (one 64-lane workgroup per (tile, 8x8 cell), any
- * tile_size; live_bits NULL: every entry of a cell's evaluated prefix).
+ * pixel no entry reaches gets 0.  The kernels replay the colour forward over
+ * its saved state (gs_replay_frame).
  * Channels go in chunks of GS_FEATURE_CHUNK = 4, the payload width of the
  * colour pass (r, g, b, z), so a chunk's backward fits the 40-byte partial
  * and everything behind it.  `features` is the [n, C] input staged
@@ -439,16 +466,7 @@ gs_status gs_blend_backward_lane_stats(const gs_blend_bwd_args *a, uint64_t *his
 #define GS_FEATURE_CHUNK 4
 #define GS_MAX_FEATURE_CHANNELS 256
 typedef struct gs_feature_fwd_args {
-  gs_camera cam;                /* the colour forward's (bg is not read) */
-  int32_t tiles_x, tiles_y;
-  const uint32_t *ranges;       /* as gs_blend_fwd_args, after that forward */
-  const uint32_t *sorted_gauss;
-  const float *records;
-  const uint32_t *cell_neval;   /* gs_blend_fwd_args.cell_neval, as written */
-  const uint64_t *live_bits;    /* gs_blend_fwd_args.live_bits, as written, or NULL */
-  int64_t live_words;
-  int32_t num_pairs;            /* T */
-  int32_t num_gaussians;        /* n: the rows of a staged chunk */
+  gs_replay_frame f;            /* the colour forward's saved state */
   int32_t channels;             /* C in 1..GS_MAX_FEATURE_CHANNELS */
   const float *features;        /* [ceil(C/4), n, 4] staged, 16-byte aligned */
   float *out;                   /* [C, H, W]: every pixel written */
@@ -469,16 +487,7 @@ gs_status gs_blend_features_forward(const gs_feature_fwd_args *a, gs_stream_t st
  * dF2, dF3}, and sets slot_live[G e + q] = 1 (G = cell_count, q the cell's
  * index in the batch, e the entry's gradient slot).  No atomics. */
 typedef struct gs_feature_bwd_args {
-  gs_camera cam;
-  int32_t tiles_x, tiles_y;
-  const uint32_t *ranges;
-  const uint32_t *sorted_gauss;
-  const float *records;         /* with pair offsets (gs_bin_emit) */
-  const uint32_t *cell_neval;
-  const uint64_t *live_bits;    /* or NULL */
-  int64_t live_words;
-  int32_t num_pairs;            /* T */
-  int32_t num_gaussians;
+  gs_replay_frame f;            /* the colour forward's saved state */
   int32_t channels;             /* C */
   int32_t chunk;                /* 0 .. ceil(C/4) - 1: channels [4 chunk, 4 chunk + 4) */
   const float *features;        /* the forward's staged input */
@@ -519,10 +528,8 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
 
 /* ---- Per-Gaussian blend contribution statistics ---------------------------
  * How much each Gaussian contributes to a frame: a third replay of the
- * colour forward (ranges / sorted_gauss / records with pair offsets /
- * cell_neval / live_bits, as the feature kernels; any tile_size; live_bits
- * NULL: every entry of a cell's evaluated prefix), one 64-lane workgroup per
- * (tile, 8x8 cell) of the cell batch [cell_begin, cell_begin + cell_count).
+ * colour forward (gs_replay_frame), one 64-lane workgroup per (tile, 8x8
+ * cell) of the cell batch [cell_begin, cell_begin + cell_count).
  * With c the forward's own contribution weight of an entry at a pixel
  * (c = (1 - A) alpha; +0 for a lane outside the tile or image, a skipped
  * pair or a terminated pixel), every replayed (entry, cell) writes
@@ -542,16 +549,7 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
  * filled with -1 / 0. */
 #define GS_CONTRIB_STRIDE 4
 typedef struct gs_contrib_args {
-  gs_camera cam;
-  int32_t tiles_x, tiles_y;
-  const uint32_t *ranges;
-  const uint32_t *sorted_gauss;
-  const float *records;         /* with pair offsets (gs_bin_emit) */
-  const uint32_t *cell_neval;
-  const uint64_t *live_bits;    /* or NULL */
-  int64_t live_words;
-  int32_t num_pairs;            /* T */
-  int32_t num_gaussians;        /* n */
+  gs_replay_frame f;            /* the colour forward's saved state */
   float *partials;              /* [T, G, GS_CONTRIB_STRIDE], 16-byte aligned */
   uint8_t *slot_live;           /* [T, G], zeroed by the caller */
   int32_t cell_begin;           /* the batch's first cell */
@@ -589,9 +587,7 @@ gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t str
 /* ---- Depth distortion and median depth through the blend -------------------
  * How spread out along the ray a pixel's contributors are, and the depth of
  * the one surface at which its opacity crosses one half: a fourth replay of
- * the colour forward (ranges / sorted_gauss / records / cell_neval /
- * live_bits, as the feature kernels; any tile_size; live_bits NULL: every
- * entry of a cell's evaluated prefix), one 64-lane workgroup per (tile, 8x8
+ * the colour forward (gs_replay_frame), one 64-lane workgroup per (tile, 8x8
  * cell), lane = pixel.  With c_i the forward's own contribution weight of
  * entry i of the pixel's tile list (c = (1 - A) alpha, A = A + c; +0 for a
  * skipped pair, a terminated pixel, or a lane outside the tile or image),
@@ -622,16 +618,7 @@ gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t str
  * 0 / -1.  A NULL required pointer, or near / far neither both zero nor
  * finite with 0 < near < far: GS_ERR_INVALID_ARG before any HIP call. */
 typedef struct gs_distortion_fwd_args {
-  gs_camera cam;                /* the colour forward's (bg is not read) */
-  int32_t tiles_x, tiles_y;
-  const uint32_t *ranges;       /* as gs_blend_fwd_args, after that forward */
-  const uint32_t *sorted_gauss;
-  const float *records;
-  const uint32_t *cell_neval;   /* gs_blend_fwd_args.cell_neval, as written */
-  const uint64_t *live_bits;    /* gs_blend_fwd_args.live_bits, as written, or NULL */
-  int64_t live_words;
-  int32_t num_pairs;            /* T */
-  int32_t num_gaussians;        /* n */
+  gs_replay_frame f;            /* the colour forward's saved state */
   float near, far;              /* both 0: linear depth; else the inverse map's planes */
   float *distortion;            /* [H, W] */
   float *moments;               /* [2, H, W]: A_n, S_n */
@@ -659,16 +646,7 @@ gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream
  * colour pass's sums (the three +0 leave its colour sums' bits alone), and
  * the projection backward, its pose form included, chains d_z. */
 typedef struct gs_distortion_bwd_args {
-  gs_camera cam;
-  int32_t tiles_x, tiles_y;
-  const uint32_t *ranges;
-  const uint32_t *sorted_gauss;
-  const float *records;         /* with pair offsets (gs_bin_emit) */
-  const uint32_t *cell_neval;
-  const uint64_t *live_bits;    /* or NULL */
-  int64_t live_words;
-  int32_t num_pairs;            /* T */
-  int32_t num_gaussians;
+  gs_replay_frame f;            /* the colour forward's saved state */
   float near, far;              /* the forward's */
   const float *distortion;      /* [H, W] the forward's output, unmodified */
   const float *moments;         /* [2, H, W] the forward's */

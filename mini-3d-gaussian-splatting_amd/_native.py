@@ -120,20 +120,40 @@ GS_FEATURE_CHUNK = 4  # channels per feature chunk: the colour pass's payload wi
 GS_MAX_FEATURE_CHANNELS = 256
 
 
-class GsFeatureFwdArgs(C.Structure):
+class GsReplayFrame(C.Structure):
+    """gs_replay_frame: the colour forward's saved state, the first member `f` of every replay's arguments
+    (anonymous there: a.cam, a.ranges, ... read and write through it)."""
     _fields_ = [
         ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
         ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
         ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+    ]
+
+
+class _ReplayArgs(C.Structure):
+    """Base of the five argument structs that begin with ("f", GsReplayFrame).  By position they take the
+    frame and then their own fields, or, as when each spelled the frame's fields out itself, the frame's
+    eleven values in place of it."""
+
+    def __init__(self, *args, **kw):
+        if args and not isinstance(args[0], GsReplayFrame):
+            k = len(GsReplayFrame._fields_)
+            args = (GsReplayFrame(*args[:k]),) + args[k:]
+        super().__init__(*args, **kw)
+
+
+class GsFeatureFwdArgs(_ReplayArgs):
+    _anonymous_ = ("f",)
+    _fields_ = [
+        ("f", GsReplayFrame),
         ("channels", C.c_int32), ("features", _vp), ("out", _vp),
     ]
 
 
-class GsFeatureBwdArgs(C.Structure):
+class GsFeatureBwdArgs(_ReplayArgs):
+    _anonymous_ = ("f",)
     _fields_ = [
-        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
-        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
-        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("f", GsReplayFrame),
         ("channels", C.c_int32), ("chunk", C.c_int32), ("features", _vp), ("out", _vp), ("g_out", _vp),
         ("pair_grads", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32), ("cell_count", C.c_int32),
     ]
@@ -151,11 +171,10 @@ class GsFeatureGatherArgs(C.Structure):
 GS_CONTRIB_STRIDE = 4  # floats per contribution partial: (sum, max, count, reserved), one 16-byte store
 
 
-class GsContribArgs(C.Structure):
+class GsContribArgs(_ReplayArgs):
+    _anonymous_ = ("f",)
     _fields_ = [
-        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
-        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
-        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("f", GsReplayFrame),
         ("partials", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32), ("cell_count", C.c_int32),
         ("dominant_id", _vp), ("dominant_weight", _vp),
     ]
@@ -169,21 +188,19 @@ class GsContribGatherArgs(C.Structure):
     ]
 
 
-class GsDistortionFwdArgs(C.Structure):
+class GsDistortionFwdArgs(_ReplayArgs):
+    _anonymous_ = ("f",)
     _fields_ = [
-        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
-        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
-        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("f", GsReplayFrame),
         ("near", C.c_float), ("far", C.c_float), ("distortion", _vp), ("moments", _vp),
         ("median_depth", _vp), ("median_id", _vp),
     ]
 
 
-class GsDistortionBwdArgs(C.Structure):
+class GsDistortionBwdArgs(_ReplayArgs):
+    _anonymous_ = ("f",)
     _fields_ = [
-        ("cam", GsCamera), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("ranges", _vp),
-        ("sorted_gauss", _vp), ("records", _vp), ("cell_neval", _vp), ("live_bits", _vp),
-        ("live_words", C.c_int64), ("num_pairs", C.c_int32), ("num_gaussians", C.c_int32),
+        ("f", GsReplayFrame),
         ("near", C.c_float), ("far", C.c_float), ("distortion", _vp), ("moments", _vp),
         ("g_distortion", _vp), ("pair_grads", _vp), ("slot_live", _vp), ("cell_begin", C.c_int32),
         ("cell_count", C.c_int32),

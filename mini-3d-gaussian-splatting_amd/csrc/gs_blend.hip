@@ -659,7 +659,8 @@ gs_status blend_backward(const gs_blend_bwd_args *a, float *abs_grads, const cha
   if (a->num_pairs < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs", what);
   gs_blend_bwd_args b = *a;
   long long blocks;
-  if (const gs_status st = cell_batch(b, what, &blocks)) return st;
+  if (const gs_status st = cell_batch(b.cam.tile_size, b.tiles_x, b.tiles_y, b.cell_begin, b.cell_count, what, &blocks))
+    return st;
   hipStream_t s = (hipStream_t)stream;
   const bool t16 = b.cam.tile_size == GS_DEFAULT_TILE && b.cell_count == cells_per_tile(b.cam.tile_size);
   if (abs_grads) {

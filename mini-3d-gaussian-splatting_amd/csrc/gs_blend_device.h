@@ -179,16 +179,16 @@ bool cell_grid(int tiles_x, int tiles_y, int ncell, long long *blocks, long long
   return *blocks * layers * kWave <= 0xffffffffLL;
 }
 
-// A launch's cell batch [cell_begin, cell_begin + cell_count) of b, defaulted
+// A launch's cell batch [cell_begin, cell_begin + cell_count), defaulted
 // (0, 0: every cell, one batch) and checked, and its grid.
-template <class Args>
-gs_status cell_batch(Args &b, const char *me, long long *blocks) {
-  const int cells = cells_per_tile(b.cam.tile_size);
-  if (b.cell_count == 0 && b.cell_begin == 0) b.cell_count = cells;
-  if (b.cell_begin < 0 || b.cell_count < 1 || b.cell_begin + b.cell_count > cells)
+gs_status cell_batch(int tile_size, int tiles_x, int tiles_y, int cell_begin, int32_t &cell_count,
+                     const char *me, long long *blocks) {
+  const int cells = cells_per_tile(tile_size);
+  if (cell_count == 0 && cell_begin == 0) cell_count = cells;
+  if (cell_begin < 0 || cell_count < 1 || cell_begin + cell_count > cells)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: the cell batch [cell_begin, cell_begin + cell_count) must lie in "
                 "[0, gs_tile_quads(tile_size))", me);
-  if (!cell_grid(b.tiles_x, b.tiles_y, b.cell_count, blocks))
+  if (!cell_grid(tiles_x, tiles_y, cell_count, blocks))
     return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
   return GS_OK;
 }

@@ -43,37 +43,36 @@ struct Replay {
 };
 
 // The replay of this workgroup's cell, one of the ncell cells from cell0 of
-// its tile, over the forward's state in a.  false: nothing to replay (a
+// its tile, over the forward's state in f.  false: nothing to replay (a
 // padding workgroup is reported through r.tile)
-template <class Args>
-__device__ __forceinline__ bool replay_setup(Replay &r, const Args &a, int ncell, int cell0) {
-  const CellGeom cg(a.cam.tile_size);
-  const uint32_t T = (uint32_t)a.num_pairs;
+__device__ __forceinline__ bool replay_setup(Replay &r, const gs_replay_frame &f, int ncell, int cell0) {
+  const CellGeom cg(f.cam.tile_size);
+  const uint32_t T = (uint32_t)f.num_pairs;
   int qb;
   uint32_t end;
-  cell_tile(blockIdx.x, ncell, a.ranges, a.tiles_x * a.tiles_y, T, r.tile, qb, r.start, end);
+  cell_tile(blockIdx.x, ncell, f.ranges, f.tiles_x * f.tiles_y, T, r.tile, qb, r.start, end);
   r.wstop = r.nwords = 0u;
   r.inside = false;
   r.lw = nullptr;
-  if (r.tile >= a.tiles_x * a.tiles_y) return false;
+  if (r.tile >= f.tiles_x * f.tiles_y) return false;
   r.quad = cell0 + qb;
   const int lane = threadIdx.x;
-  r.tx = (uint32_t)(r.tile % a.tiles_x);
-  r.ty = (uint32_t)(r.tile / a.tiles_x);
+  r.tx = (uint32_t)(r.tile % f.tiles_x);
+  r.ty = (uint32_t)(r.tile / f.tiles_x);
   const int cx0 = (r.quad % cg.QX) * 8, cy0 = (r.quad / cg.QX) * 8;  // the cell in its tile
   r.x0 = (int)r.tx * cg.L + cx0;
   r.y0 = (int)r.ty * cg.L + cy0;
   r.px = r.x0 + (lane & 7);
   r.py = r.y0 + (lane >> 3);
   r.inside =
-      cx0 + (lane & 7) < cg.L && cy0 + (lane >> 3) < cg.L && r.px < a.cam.image_width && r.py < a.cam.image_height;
+      cx0 + (lane & 7) < cg.L && cy0 + (lane >> 3) < cg.L && r.px < f.cam.image_width && r.py < f.cam.image_height;
   if (r.start >= end) return false;
   // the cell's last evaluated entry (never past the list, whatever the word holds)
-  r.wstop = min((uint32_t)__builtin_amdgcn_readfirstlane(a.cell_neval[(size_t)r.tile * cg.cells() + r.quad]),
+  r.wstop = min((uint32_t)__builtin_amdgcn_readfirstlane(f.cell_neval[(size_t)r.tile * cg.cells() + r.quad]),
                 end - r.start);
   r.nwords = (r.wstop + 63u) >> 6;
-  if (a.live_bits)
-    r.lw = reinterpret_cast<const unsigned long long *>(a.live_bits) + (size_t)r.quad * a.live_words + r.start / 64u +
+  if (f.live_bits)
+    r.lw = reinterpret_cast<const unsigned long long *>(f.live_bits) + (size_t)r.quad * f.live_words + r.start / 64u +
            (uint32_t)r.tile;
   return r.wstop != 0u;
 }
@@ -88,19 +87,19 @@ __device__ __forceinline__ bool replay_setup(Replay &r, const Args &a, int ncell
 //   payload(gid)        the float4 it carries for Gaussian gid,
 //   entry(payload, c, A) its accumulation, A the sum before the entry,
 // and gets back the pixel's A after the last one.
-template <class Args, class Payload, class Entry>
-__device__ __forceinline__ float word_walk(const Replay &r, const Args &a, float4 *s_rec, Payload payload,
+template <class Payload, class Entry>
+__device__ __forceinline__ float word_walk(const Replay &r, const gs_replay_frame &f, float4 *s_rec, Payload payload,
                                            Entry entry) {
   const int lane = threadIdx.x;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  const uint32_t ngauss = (uint32_t)f.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(f.records);
   const float fx = (float)r.px, fy = (float)r.py;
   float A = 0.f, T1 = 1.f;
   bool run = r.inside;  // A < 0.995 so far; lanes outside the tile or image never run
   float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f), n1 = n0, nf = n0;
   auto fetch = [&](uint32_t wd, unsigned long long m) {
     if ((m >> lane) & 1ull) {
-      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+      const uint32_t gid = min(f.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
       n0 = recs[3 * (size_t)gid];
       n1 = recs[3 * (size_t)gid + 1];
       nf = payload(gid);
@@ -184,12 +183,12 @@ struct Rec2 {  // (mx my h00 h11) (ho o slot p0)
 //   payload(gid, r2)      the float4 it stages for Gaussian gid (r2: its third record),
 //   phase_a(kk, rec, st)  entry kk of the group for this pixel: rec its staged record, st its ChainStep,
 //   phase_b(k)            the group's k entries reduced and stored, their records at s_wrec positions 0 .. k - 1.
-template <class Rec, class Args, class Payload, class PhaseA, class PhaseB>
-__device__ __forceinline__ void group_walk(const Replay &r, const Args &a, float4 *s_wrec, Payload payload,
+template <class Rec, class Payload, class PhaseA, class PhaseB>
+__device__ __forceinline__ void group_walk(const Replay &r, const gs_replay_frame &f, float4 *s_wrec, Payload payload,
                                            PhaseA phase_a, PhaseB phase_b) {
   const int lane = threadIdx.x;
-  const uint32_t ngauss = (uint32_t)a.num_gaussians;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  const uint32_t ngauss = (uint32_t)f.num_gaussians;
+  const float4 *recs = reinterpret_cast<const float4 *>(f.records);
   const float fx = (float)r.px, fy = (float)r.py;
   float A = 0.f, T1 = 1.f;
   // `run` is the forward's "A < 0.995 before this entry", carried from the
@@ -198,7 +197,7 @@ __device__ __forceinline__ void group_walk(const Replay &r, const Args &a, float
   float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0, rp = r0;
   auto fetch = [&](uint32_t wd, unsigned long long m) {
     if ((m >> lane) & 1ull) {
-      const uint32_t gid = min(a.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
+      const uint32_t gid = min(f.sorted_gauss[r.start + 64u * wd + (uint32_t)lane], ngauss - 1u);
       r0 = recs[3 * (size_t)gid];
       r1 = recs[3 * (size_t)gid + 1];
       r2 = recs[3 * (size_t)gid + 2];
@@ -327,7 +326,7 @@ __device__ __forceinline__ void phase_b_geometry(const Replay &r, const Args &a,
       // dmu = -(2 q00 Sx + qo Sy, qo Sx + 2 q11 Sy)
       const float g0 = -(2.f * q00 * Sx + qo * Sy), g1 = -(qo * Sx + 2.f * q11 * Sy);
       const size_t sq = (size_t)slot * (uint32_t)a.cell_count + (uint32_t)(r.quad - a.cell_begin);
-      if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+      if (slot < (uint32_t)a.f.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
         float *out = a.pair_grads + sq * GS_PARTIAL_STRIDE;  // (dense 40-B partials, 8-B aligned: f4_u8)
         *reinterpret_cast<f4_u8 *>(out) = f4_u8{g0, g1, g2, g3};
         *reinterpret_cast<f4_u8 *>(out + 4) = f4_u8{g4, g5, t.x, t.y};
@@ -344,15 +343,15 @@ __device__ __forceinline__ void phase_b_geometry(const Replay &r, const Args &a,
 __global__ __launch_bounds__(kWave) void k_feat_fwd(gs_feature_fwd_args a) {
   __shared__ float4 s_rec[kWave * 3];  // per entry: (mx my h00 h11) (ho o - -) (f0 f1 f2 f3), h = -q/2
   Replay r;
-  const CellGeom cg(a.cam.tile_size);
-  const bool any = replay_setup(r, a, cg.cells(), 0);
-  if (r.tile >= a.tiles_x * a.tiles_y) return;
+  const CellGeom cg(a.f.cam.tile_size);
+  const bool any = replay_setup(r, a.f, cg.cells(), 0);
+  if (r.tile >= a.f.tiles_x * a.f.tiles_y) return;
   const uint32_t chunk = blockIdx.y;
-  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)chunk * (uint32_t)a.num_gaussians;
+  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)chunk * (uint32_t)a.f.num_gaussians;
   float f0 = 0.f, f1 = 0.f, f2 = 0.f, f3 = 0.f;
   if (any)
     word_walk(
-        r, a, s_rec, [&](uint32_t gid) { return feat[gid]; },
+        r, a.f, s_rec, [&](uint32_t gid) { return feat[gid]; },
         [&](const float4 &fv, float c, float) {
           f0 = __builtin_fmaf(c, fv.x, f0);
           f1 = __builtin_fmaf(c, fv.y, f1);
@@ -360,8 +359,8 @@ __global__ __launch_bounds__(kWave) void k_feat_fwd(gs_feature_fwd_args a) {
           f3 = __builtin_fmaf(c, fv.w, f3);
         });
   if (!r.inside) return;
-  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
-  const size_t p = (size_t)r.py * a.cam.image_width + r.px;
+  const size_t HW = (size_t)a.f.cam.image_width * a.f.cam.image_height;
+  const size_t p = (size_t)r.py * a.f.cam.image_width + r.px;
   const uint32_t ch = chunk * GS_FEATURE_CHUNK, C = (uint32_t)a.channels;
   a.out[(size_t)ch * HW + p] = f0;
   if (ch + 1u < C) a.out[(size_t)(ch + 1u) * HW + p] = f1;
@@ -380,13 +379,13 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 6))) v
   __shared__ float4 s_pg[kWave];               // per pixel: dL/dout of the chunk's four channels
   __shared__ float2 s_wrec[kBwdGroup * 6];     // the group's records: (mx my h00 h11) (ho o f0 f1) (f2 f3 slot -)
   Replay r;
-  if (!replay_setup(r, a, a.cell_count, a.cell_begin)) return;
+  if (!replay_setup(r, a.f, a.cell_count, a.cell_begin)) return;
   const int lane = threadIdx.x;
-  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)a.chunk * (uint32_t)a.num_gaussians;
+  const float4 *feat = reinterpret_cast<const float4 *>(a.features) + (size_t)a.chunk * (uint32_t)a.f.num_gaussians;
   // the pixel's cotangents and outputs of this chunk (channels past C: zero;
   // lanes outside read pixel 0, unused)
-  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
-  const size_t p = r.inside ? (size_t)r.py * a.cam.image_width + r.px : 0;
+  const size_t HW = (size_t)a.f.cam.image_width * a.f.cam.image_height;
+  const size_t p = r.inside ? (size_t)r.py * a.f.cam.image_width + r.px : 0;
   const uint32_t ch = (uint32_t)a.chunk * GS_FEATURE_CHUNK, C = (uint32_t)a.channels;
   float gF[GS_FEATURE_CHUNK], oF[GS_FEATURE_CHUNK];
 #pragma unroll
@@ -404,7 +403,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 6))) v
   float PG = -K;
   float4 *wrec = reinterpret_cast<float4 *>(s_wrec);
   group_walk<Rec3>(
-      r, a, wrec, [&](uint32_t gid, const float4 &) { return feat[gid]; },
+      r, a.f, wrec, [&](uint32_t gid, const float4 &) { return feat[gid]; },
       [&](int kk, const float4 *rec, const ChainStep &st) {
         const float4 r1v = rec[1];
         const float2 f23 = make_float2(rec[2].x, rec[2].y);
@@ -500,14 +499,14 @@ __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
   __shared__ float s_c[kBwdGroup][kCtbRow];  // per group entry and pixel: c
   __shared__ float4 s_wrec[kBwdGroup * 2];   // the group's records: (mx my h00 h11) (ho o slot gid)
   Replay r;
-  const bool any = replay_setup(r, a, a.cell_count, a.cell_begin);
-  if (r.tile >= a.tiles_x * a.tiles_y) return;
+  const bool any = replay_setup(r, a.f, a.cell_count, a.cell_begin);
+  if (r.tile >= a.f.tiles_x * a.f.tiles_y) return;
   const int lane = threadIdx.x;
   float best = 0.f;
   int best_id = -1;
   if (any)
     group_walk<Rec2>(
-        r, a, s_wrec, [](uint32_t gid, const float4 &) { return make_float4(__uint_as_float(gid), 0.f, 0.f, 0.f); },
+        r, a.f, s_wrec, [](uint32_t gid, const float4 &) { return make_float4(__uint_as_float(gid), 0.f, 0.f, 0.f); },
         [&](int kk, const float4 *rec, const ChainStep &st) {
           const float c = st.p.c;
           if (c > best) {
@@ -532,7 +531,7 @@ __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
             cnt = oct_sum(cnt);  // (small integers: exact)
             if (col == 0) {
               const uint32_t slot = Rec2::slot(s_wrec + 2 * j);
-              if (slot < (uint32_t)a.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
+              if (slot < (uint32_t)a.f.num_pairs) {  // (a slot of this frame's T; a corrupt record writes nothing)
                 const size_t sq = (size_t)slot * (uint32_t)a.cell_count + (uint32_t)(r.quad - a.cell_begin);
                 reinterpret_cast<float4 *>(a.partials)[sq] = make_float4(sum, mx, cnt, 0.f);
                 a.slot_live[sq] = 1;
@@ -541,7 +540,7 @@ __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
           }
         });
   if (a.dominant_id && r.inside) {
-    const size_t p = (size_t)r.py * a.cam.image_width + r.px;
+    const size_t p = (size_t)r.py * a.f.cam.image_width + r.px;
     a.dominant_id[p] = best_id;
     a.dominant_weight[p] = best;
   }
@@ -634,15 +633,15 @@ template <bool kInv>
 __global__ __launch_bounds__(kWave) void k_dist_fwd(gs_distortion_fwd_args a, float kappa) {
   __shared__ float4 s_rec[kWave * 3];  // per entry: (mx my h00 h11) (ho o - -) (z q r id), h = -q/2
   Replay r;
-  const CellGeom cg(a.cam.tile_size);
-  const bool any = replay_setup(r, a, cg.cells(), 0);
-  if (r.tile >= a.tiles_x * a.tiles_y) return;
-  const float4 *recs = reinterpret_cast<const float4 *>(a.records);
+  const CellGeom cg(a.f.cam.tile_size);
+  const bool any = replay_setup(r, a.f, cg.cells(), 0);
+  if (r.tile >= a.f.tiles_x * a.f.tiles_y) return;
+  const float4 *recs = reinterpret_cast<const float4 *>(a.f.records);
   float A = 0.f, S = 0.f, D = 0.f, med_z = 0.f, zf = 0.f, rf = 1.f;
   int med_id = -1;
   if (any)
     A = word_walk(
-        r, a, s_rec, [&](uint32_t gid) { return dist_payload(recs[3 * (size_t)gid + 2].y, gid, kappa); },
+        r, a.f, s_rec, [&](uint32_t gid) { return dist_payload(recs[3 * (size_t)gid + 2].y, gid, kappa); },
         [&](const float4 &fv, float c, float Ap) {
           // until the first contributor (A == 0) the reference follows the entry: m = 0, and c = +0
           const bool have = Ap > 0.f;
@@ -660,8 +659,8 @@ __global__ __launch_bounds__(kWave) void k_dist_fwd(gs_distortion_fwd_args a, fl
           }
         });
   if (!r.inside) return;
-  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
-  const size_t p = (size_t)r.py * a.cam.image_width + r.px;
+  const size_t HW = (size_t)a.f.cam.image_width * a.f.cam.image_height;
+  const size_t p = (size_t)r.py * a.f.cam.image_width + r.px;
   a.distortion[p] = 2.f * D;
   a.moments[p] = A;
   a.moments[HW + p] = S;
@@ -693,11 +692,11 @@ __global__ __launch_bounds__(kWave) void k_dist_bwd(gs_distortion_bwd_args a, fl
   __shared__ float s_dm[kBwdGroup][kBwdRow];   // ... and dL/dm
   __shared__ float2 s_wrec[kBwdGroup * 6];     // the group's records: (mx my h00 h11) (ho o z q) (r - slot -)
   Replay r;
-  if (!replay_setup(r, a, a.cell_count, a.cell_begin)) return;
+  if (!replay_setup(r, a.f, a.cell_count, a.cell_begin)) return;
   const int lane = threadIdx.x;
   // the pixel's cotangent and the forward's state (lanes outside read pixel 0, unused)
-  const size_t HW = (size_t)a.cam.image_width * a.cam.image_height;
-  const size_t p = r.inside ? (size_t)r.py * a.cam.image_width + r.px : 0;
+  const size_t HW = (size_t)a.f.cam.image_width * a.f.cam.image_height;
+  const size_t p = r.inside ? (size_t)r.py * a.f.cam.image_width + r.px : 0;
   const float g2 = r.inside ? 2.f * a.g_distortion[p] : 0.f;
   const float An = a.moments[p], Sn = a.moments[HW + p];
   // PG = P - K as one running sum (k_feat_bwd), K = 2 g D
@@ -705,7 +704,7 @@ __global__ __launch_bounds__(kWave) void k_dist_bwd(gs_distortion_bwd_args a, fl
   float S = 0.f, zf = 0.f, rf = 1.f;
   float4 *wrec = reinterpret_cast<float4 *>(s_wrec);
   group_walk<Rec3>(
-      r, a, wrec,
+      r, a.f, wrec,
       [&](uint32_t gid, const float4 &r2) {
         const float4 zqr = dist_payload(r2.y, gid, kappa);
         return make_float4(zqr.x, zqr.y, zqr.z, 0.f);  // (the id is not staged)
@@ -752,7 +751,45 @@ float near_far_kappa(float near, float far) {
   return (near == 0.f && far == 0.f) ? 0.f : (float)((double)far * near / ((double)far - near));
 }
 
-bool channels_ok(int channels) { return channels >= 1 && channels <= GS_MAX_FEATURE_CHANNELS; }
+// The fault in a pass's own scalars, as the message it is reported with, or nullptr
+const char *channels_fault(int channels, int chunk) {
+  if (channels < 1 || channels > GS_MAX_FEATURE_CHANNELS) return "%s: channels must be in [1, GS_MAX_FEATURE_CHANNELS]";
+  if (chunk < 0 || chunk >= (int)div_up(channels, GS_FEATURE_CHUNK))
+    return "%s: chunk must be in [0, ceil(channels / 4))";
+  return nullptr;
+}
+
+const char *near_far_fault(float near, float far) {
+  if (near_far_ok(near, far)) return nullptr;
+  return "%s: near / far must both be 0 (linear depth) or finite with 0 < near < far";
+}
+
+// The checks every replay makes of the colour forward's state, in one order:
+// the camera, the tile grid, own_fault (the pass's own scalars, above), the
+// frame's buffers, the counts.  list_always: the pass reads sorted_gauss
+// whatever num_pairs is (the backwards); otherwise only a frame with entries
+// needs it.  min_gaussians: 1 for the passes that index rows of a
+// per-Gaussian input, 0 for those that accept an empty model.
+gs_status replay_frame_check(const gs_replay_frame &f, const char *me, bool list_always, int min_gaussians,
+                             const char *own_fault = nullptr) {
+  if (!cam_ok(f.cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
+  if (!tiles_match(f.cam, f.tiles_x, f.tiles_y))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
+  if (own_fault) return gs_internal_fail(GS_ERR_INVALID_ARG, own_fault, me);
+  if (!f.ranges || !f.records || !f.cell_neval || (f.live_bits && f.live_words <= 0) ||
+      ((list_always || f.num_pairs > 0) && !f.sorted_gauss))
+    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (f.num_pairs < 0 || f.num_gaussians < min_gaussians)
+    return gs_internal_fail(GS_ERR_INVALID_ARG, min_gaussians > 0 ? "%s: negative num_pairs or no Gaussians"
+                                                                  : "%s: negative num_pairs or num_gaussians", me);
+  return GS_OK;
+}
+
+// cell_batch for a replay's arguments b: its cell_begin / cell_count over its frame's tiles
+template <class Args>
+gs_status replay_cell_batch(Args &b, const char *me, long long *blocks) {
+  return cell_batch(b.f.cam.tile_size, b.f.tiles_x, b.f.tiles_y, b.cell_begin, b.cell_count, me, blocks);
+}
 
 }  // namespace
 
@@ -762,19 +799,11 @@ extern "C" {
 gs_status gs_blend_features_forward(const gs_feature_fwd_args *a, gs_stream_t stream) {
   const char *me = "gs_blend_features_forward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
-  if (!channels_ok(a->channels))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: channels must be in [1, GS_MAX_FEATURE_CHANNELS]", me);
-  if (!a->ranges || !a->records || !a->cell_neval || !a->features || !a->out || (a->live_bits && a->live_words <= 0) ||
-      (a->num_pairs > 0 && !a->sorted_gauss))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->num_pairs < 0 || a->num_gaussians < 1)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
+  if (const gs_status st = replay_frame_check(a->f, me, false, 1, channels_fault(a->channels, 0))) return st;
+  if (!a->features || !a->out) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
   const long long chunks = div_up(a->channels, GS_FEATURE_CHUNK);
   long long blocks;
-  if (!cell_grid(a->tiles_x, a->tiles_y, cells_per_tile(a->cam.tile_size), &blocks, chunks))
+  if (!cell_grid(a->f.tiles_x, a->f.tiles_y, cells_per_tile(a->f.cam.tile_size), &blocks, chunks))
     return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
   k_feat_fwd<<<dim3((unsigned)blocks, (unsigned)chunks), kWave, 0, (hipStream_t)stream>>>(*a);
   return gs_internal_check_launch(me);
@@ -783,21 +812,12 @@ gs_status gs_blend_features_forward(const gs_feature_fwd_args *a, gs_stream_t st
 gs_status gs_blend_features_backward(const gs_feature_bwd_args *a, gs_stream_t stream) {
   const char *me = "gs_blend_features_backward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
-  if (!channels_ok(a->channels))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: channels must be in [1, GS_MAX_FEATURE_CHANNELS]", me);
-  if (a->chunk < 0 || a->chunk >= (int)div_up(a->channels, GS_FEATURE_CHUNK))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: chunk must be in [0, ceil(channels / 4))", me);
-  if (!a->ranges || !a->sorted_gauss || !a->records || !a->cell_neval || !a->features || !a->out || !a->g_out ||
-      !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
+  if (const gs_status st = replay_frame_check(a->f, me, true, 1, channels_fault(a->channels, a->chunk))) return st;
+  if (!a->features || !a->out || !a->g_out || !a->pair_grads || !a->slot_live)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->num_pairs < 0 || a->num_gaussians < 1)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
   gs_feature_bwd_args b = *a;
   long long blocks;
-  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
+  if (const gs_status st = replay_cell_batch(b, me, &blocks)) return st;
   k_feat_bwd<<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b);
   return gs_internal_check_launch(me);
 }
@@ -829,22 +849,16 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
 gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream) {
   const char *me = "gs_blend_contributions";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
-  if (a->num_pairs < 0 || a->num_gaussians < 0)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or num_gaussians", me);
-  if (!a->ranges || !a->records || !a->cell_neval || !a->partials || !a->slot_live ||
-      (a->live_bits && a->live_words <= 0) || (a->num_pairs > 0 && !a->sorted_gauss))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
+  if (const gs_status st = replay_frame_check(a->f, me, false, 0)) return st;
+  if (!a->partials || !a->slot_live) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
   if (!a->dominant_id != !a->dominant_weight)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: dominant_id and dominant_weight go together", me);
   gs_contrib_args b = *a;
   long long blocks;
-  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
-  if (b.num_gaussians == 0 || b.num_pairs == 0) {
+  if (const gs_status st = replay_cell_batch(b, me, &blocks)) return st;
+  if (b.f.num_gaussians == 0 || b.f.num_pairs == 0) {
     if (!b.dominant_id) return GS_OK;
-    const long long pixels = (long long)b.cam.image_width * b.cam.image_height;
+    const long long pixels = (long long)b.f.cam.image_width * b.f.cam.image_height;
     k_contrib_empty<<<div_up(pixels, kBlock), kBlock, 0, (hipStream_t)stream>>>(b.dominant_id, b.dominant_weight, pixels);
     return gs_internal_check_launch(me);
   }
@@ -855,21 +869,14 @@ gs_status gs_blend_contributions(const gs_contrib_args *a, gs_stream_t stream) {
 gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream_t stream) {
   const char *me = "gs_blend_distortion_forward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
-  if (!near_far_ok(a->near, a->far))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: near / far must both be 0 (linear depth) or finite with 0 < near < far", me);
-  if (!a->ranges || !a->records || !a->cell_neval || !a->distortion || !a->moments || !a->median_depth ||
-      !a->median_id || (a->live_bits && a->live_words <= 0) || (a->num_pairs > 0 && !a->sorted_gauss))
+  if (const gs_status st = replay_frame_check(a->f, me, false, 0, near_far_fault(a->near, a->far))) return st;
+  if (!a->distortion || !a->moments || !a->median_depth || !a->median_id)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->num_pairs < 0 || a->num_gaussians < 0)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or num_gaussians", me);
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
   long long blocks;
-  if (!cell_grid(a->tiles_x, a->tiles_y, cells_per_tile(a->cam.tile_size), &blocks))
+  if (!cell_grid(a->f.tiles_x, a->f.tiles_y, cells_per_tile(a->f.cam.tile_size), &blocks))
     return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: too many tiles", me);
-  if (a->num_gaussians == 0 || a->num_pairs == 0) {
-    const long long pixels = (long long)a->cam.image_width * a->cam.image_height;
+  if (a->f.num_gaussians == 0 || a->f.num_pairs == 0) {
+    const long long pixels = (long long)a->f.cam.image_width * a->f.cam.image_height;
     k_dist_empty<<<div_up(pixels, kBlock), kBlock, 0, (hipStream_t)stream>>>(*a, pixels);
     return gs_internal_check_launch(me);
   }
@@ -884,19 +891,12 @@ gs_status gs_blend_distortion_forward(const gs_distortion_fwd_args *a, gs_stream
 gs_status gs_blend_distortion_backward(const gs_distortion_bwd_args *a, gs_stream_t stream) {
   const char *me = "gs_blend_distortion_backward";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
-  if (!near_far_ok(a->near, a->far))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: near / far must both be 0 (linear depth) or finite with 0 < near < far", me);
-  if (!a->ranges || !a->sorted_gauss || !a->records || !a->cell_neval || !a->distortion || !a->moments ||
-      !a->g_distortion || !a->pair_grads || !a->slot_live || (a->live_bits && a->live_words <= 0))
+  if (const gs_status st = replay_frame_check(a->f, me, true, 1, near_far_fault(a->near, a->far))) return st;
+  if (!a->distortion || !a->moments || !a->g_distortion || !a->pair_grads || !a->slot_live)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->num_pairs < 0 || a->num_gaussians < 1)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative num_pairs or no Gaussians", me);
-  if (!cam_ok(a->cam)) return gs_internal_fail(GS_ERR_UNSUPPORTED, kCamMsg, me);
-  if (!tiles_match(a->cam, a->tiles_x, a->tiles_y))
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: tiles_x/tiles_y do not match the image", me);
   gs_distortion_bwd_args b = *a;
   long long blocks;
-  if (const gs_status st = cell_batch(b, me, &blocks)) return st;
+  if (const gs_status st = replay_cell_batch(b, me, &blocks)) return st;
   const float kappa = near_far_kappa(b.near, b.far);
   if (kappa != 0.f)
     k_dist_bwd<true><<<(unsigned)blocks, kWave, 0, (hipStream_t)stream>>>(b, kappa);

@@ -146,12 +146,13 @@ LIVE_BUDGET_BYTES = int(os.environ.get("GS_LIVE_BUDGET", str(1 << 30)))
 _ALWAYS_ONE_BATCH = 4  # cells
 
 
-def cell_batch(cells: int, entries: int) -> int:
+def cell_batch(cells: int, entries: int, slot_bytes: int = 41) -> int:
     """Cells per blend-backward batch for a frame of `entries` list entries:
     every cell at once unless the [entries, cells] partials (40 B) and flags
     (1 B) would exceed PARTIAL_BUDGET_BYTES; batches are summed in order by
-    gs_gather_partials (deterministic, bounded memory)."""
-    per = 41 * max(int(entries), 1)
+    gs_gather_partials (deterministic, bounded memory).  slot_bytes: the
+    scratch per (entry, cell) of another pass."""
+    per = slot_bytes * max(int(entries), 1)
     if cells <= _ALWAYS_ONE_BATCH or cells * per <= PARTIAL_BUDGET_BYTES:
         return cells
     return max(1, min(cells, PARTIAL_BUDGET_BYTES // per))
@@ -452,10 +453,7 @@ class _ContributionPass:
 def contribution_cell_batch(cells: int, entries: int) -> int:
     """cell_batch's rule for the contribution pass's scratch: 16 B of partial
     and 1 B of flag per (entry, cell)."""
-    per = 17 * max(int(entries), 1)
-    if cells <= _ALWAYS_ONE_BATCH or cells * per <= PARTIAL_BUDGET_BYTES:
-        return cells
-    return max(1, min(cells, PARTIAL_BUDGET_BYTES // per))
+    return cell_batch(cells, entries, 17)
 
 
 def _contribution_pass(cam: CameraParams, fr: "_Frame", n: int, cp: _ContributionPass, dev) -> None:
@@ -478,10 +476,8 @@ def _contribution_pass(cam: CameraParams, fr: "_Frame", n: int, cp: _Contributio
     G = contribution_cell_batch(Q, T)
     partials = torch.empty((T * G, N.GS_CONTRIB_STRIDE), dtype=torch.float32, device=dev)
     flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
-    ca = N.GsContribArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                         N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
-                         0 if fr.live_bits is None else fr.live_bits.shape[1], T, n, N.ptr(partials), N.ptr(flags),
-                         0, 0, N.ptr(cp.dominant_id), N.ptr(cp.dominant_weight))
+    ca = N.GsContribArgs(replay_frame(cam, fr, n), N.ptr(partials), N.ptr(flags), 0, 0, N.ptr(cp.dominant_id),
+                         N.ptr(cp.dominant_weight))
     st = cp.stats
     if st is not None:
         ga = N.GsContribGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(partials),
@@ -538,6 +534,18 @@ def _live_words(fr) -> int:
     return 0 if fr.live_bits is None else fr.live_bits.shape[1]
 
 
+def replay_frame(cam: CameraParams, fr, n: int) -> N.GsReplayFrame:
+    """gs_replay_frame of a stage-path frame `fr` of n Gaussians: the colour
+    forward's saved state, the first member of every replay's arguments."""
+    return N.GsReplayFrame(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
+                           N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits), _live_words(fr), fr.T, n)
+
+
+def _fp32_contiguous(t: torch.Tensor) -> torch.Tensor:
+    """A cotangent as the kernels read it."""
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+
+
 def _distortion_forward(cam: CameraParams, fr: "_Frame", n: int, dp: _DistortionPass, dev) -> torch.Tensor:
     """The distortion map [H, W] of a stage-path frame, and dp's maps: one
     gs_blend_distortion_forward over the state the colour forward left in
@@ -553,62 +561,92 @@ def _distortion_forward(cam: CameraParams, fr: "_Frame", n: int, dp: _Distortion
     dp.moments = torch.empty((2, H, W), dtype=f32, device=dev)
     dp.median_depth = torch.empty((H, W), dtype=f32, device=dev)
     dp.median_id = torch.empty((H, W), dtype=torch.int32, device=dev)
-    fa = N.GsDistortionFwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                               N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits), _live_words(fr), fr.T, n,
-                               dp.near, dp.far, N.ptr(out), N.ptr(dp.moments), N.ptr(dp.median_depth),
-                               N.ptr(dp.median_id))
+    fa = N.GsDistortionFwdArgs(replay_frame(cam, fr, n), dp.near, dp.far, N.ptr(out), N.ptr(dp.moments),
+                               N.ptr(dp.median_depth), N.ptr(dp.median_id))
     StageTimer.mark("distortion_fwd")
     N.check(N.load().gs_blend_distortion_forward(C.byref(fa), _stream()), "gs_blend_distortion_forward")
     StageTimer.mark("~end_distortion_fwd")
     return out
 
 
-def _distortion_backward(lib, cam: CameraParams, fr: "_Frame", dist: _DistortionGrad, n: int, pair_grads, slot_live,
-                         sums, s) -> torch.Tensor:
+class _GradSums:
+    """One backward's per-Gaussian sums over a stage-path frame, [n,
+    GS_PAIR_GRAD_FLOATS] (allocated on first need), and what every pass needs
+    to add to them: the frame's gather arguments, whether the sums hold
+    anything yet (the next gather's `accumulate`), and the colour pass's
+    partial buffer -- with its flags while its one batch is not yet gathered."""
+    __slots__ = ("fr", "n", "dev", "_sums", "have", "partials", "flags")
+
+    def __init__(self, fr: "_Frame", n: int, dev):
+        self.fr, self.n, self.dev = fr, n, dev
+        self._sums, self.have, self.partials, self.flags = None, False, None, None
+
+    @property
+    def sums(self) -> torch.Tensor:
+        if self._sums is None:
+            self._sums = torch.empty((self.n, N.GS_PAIR_GRAD_FLOATS), dtype=torch.float32, device=self.dev)
+        return self._sums
+
+    def accumulate(self) -> int:
+        """The `accumulate` of the next gather into the sums: 0 for the first, which stores."""
+        acc, self.have = (1 if self.have else 0), True
+        return acc
+
+    def gather_args(self, pair_grads, slot_live) -> "N.GsProjectBwdArgs":
+        """gs_gather_partials' arguments for the frame's slots of (pair_grads, slot_live)."""
+        ga, fr = N.GsProjectBwdArgs(), self.fr
+        ga.g.n = self.n
+        ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
+        ga.pair_grads, ga.slot_live, ga.grad_sums = N.ptr(pair_grads), N.ptr(slot_live), N.ptr(self.sums)
+        return ga
+
+    def gather(self, lib, ga: "N.GsProjectBwdArgs", groups: int, s) -> None:
+        """One gs_gather_partials of ga's partials, `groups` per slot, into the sums."""
+        ga.partial_groups = groups
+        N.check(lib.gs_gather_partials(C.byref(ga), self.accumulate(), s), "gs_gather_partials")
+
+    def scratch(self, lib, s):
+        """(partials [T G, GS_PARTIAL_STRIDE], flags [T G]) for a pass after the
+        colour pass, G = the frame's cells per batch: the colour pass's partials
+        are gathered first if they still wait, and their buffer is reused when
+        it is large enough.  The flags are the pass's own, cleared by it before
+        every launch."""
+        rows = self.fr.T * self.fr.groups
+        if self.flags is not None:
+            self.gather(lib, self.gather_args(self.partials, self.flags), self.fr.groups, s)
+            self.flags = None
+        if self.partials is None or self.partials.shape[0] < rows:
+            self.partials = torch.empty((rows, N.GS_PARTIAL_STRIDE), dtype=torch.float32, device=self.dev)
+        return self.partials, torch.empty((rows,), dtype=torch.uint8, device=self.dev)
+
+    def for_projection(self):
+        """(pair_grads, slot_live, grad_sums) of the projection backward: the
+        colour pass's partials and flags with a buffer to sum them into, or the
+        sums gathered so far, or nothing (no blend gradient)."""
+        if self.flags is not None:
+            return self.partials, self.flags, self.sums
+        return None, None, (self._sums if self.have else None)
+
+
+def _distortion_backward(lib, cam: CameraParams, fr: "_Frame", dist: _DistortionGrad, sums: _GradSums, s) -> None:
     """The distortion's backward over a stage-path frame: per cell batch (the
     frame's own plan: fr.groups cells at a time) one
     gs_blend_distortion_backward and one gs_gather_partials that adds its
-    partials to the sums so far.  Returns grad_sums [n, 10] for the projection
-    backward.  pair_grads / slot_live: the colour pass's one-batch partials,
-    not yet gathered (gathered here first, then the buffer is reused), or
-    None; sums: the sums gathered so far (the colour pass's batches, the
-    feature pass's), or None.  The flags are this call's own scratch, cleared
-    before every launch."""
-    dev = dist.out.device
-    f32 = torch.float32
-    G, Q, T = fr.groups, cam.cells, fr.T
-    have = sums is not None
-    grad_sums = sums if have else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
-    ga = N.GsProjectBwdArgs()
-    ga.g.n = n
-    ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
-    ga.grad_sums = N.ptr(grad_sums)
-    if pair_grads is not None:
-        ga.pair_grads, ga.slot_live, ga.partial_groups = N.ptr(pair_grads), N.ptr(slot_live), G
-        N.check(lib.gs_gather_partials(C.byref(ga), 1 if have else 0, s), "gs_gather_partials")
-        have = True
-    if pair_grads is None or pair_grads.shape[0] < T * G:
-        pair_grads = torch.empty((T * G, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
-    flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
-    g_out = dist.g_out
-    if g_out.dtype != f32 or not g_out.is_contiguous():
-        g_out = g_out.to(f32).contiguous()
+    partials to `sums`."""
+    G, Q = fr.groups, cam.cells
+    pair_grads, flags = sums.scratch(lib, s)
     dp = dist.dp
-    ba = N.GsDistortionBwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                               N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits), _live_words(fr), T, n,
-                               dp.near, dp.far, N.ptr(dist.out), N.ptr(dp.moments), N.ptr(g_out), N.ptr(pair_grads),
-                               N.ptr(flags), 0, 0)
-    ga.pair_grads, ga.slot_live = N.ptr(pair_grads), N.ptr(flags)
+    g_out = _fp32_contiguous(dist.g_out)
+    ba = N.GsDistortionBwdArgs(replay_frame(cam, fr, sums.n), dp.near, dp.far, N.ptr(dist.out), N.ptr(dp.moments),
+                               N.ptr(g_out), N.ptr(pair_grads), N.ptr(flags), 0, 0)
+    ga = sums.gather_args(pair_grads, flags)
     StageTimer.mark("distortion_bwd")
     for c0 in range(0, Q, G):
         ba.cell_begin, ba.cell_count = c0, min(G, Q - c0)
-        ga.partial_groups = ba.cell_count
         flags.zero_()
         N.check(lib.gs_blend_distortion_backward(C.byref(ba), s), "gs_blend_distortion_backward")
-        N.check(lib.gs_gather_partials(C.byref(ga), 1 if have else 0, s), "gs_gather_partials")
-        have = True
+        sums.gather(lib, ga, ba.cell_count, s)
     StageTimer.mark("~end_distortion_bwd")
-    return grad_sums
 
 
 class _Frame:
@@ -1205,7 +1243,8 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     f32 = torch.float32
     s = _stream()
     cs = cam.to_struct()
-    pair_grads = slot_live = abs_sums = None
+    abs_sums = None
+    sums = _GradSums(fr, n, dev)  # (the one owner of this backward's per-Gaussian sums)
     # (statistics with abs_accum: the blend backward also writes the absolute partials, summed
     # per Gaussian right after each batch -- before the flags are cleared or another pass sets its own)
     want_abs = density is not None and density[0].abs_accum is not None
@@ -1231,7 +1270,7 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
         ba = N.GsBlendBwdArgs(cs, cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
                               N.ptr(fr.records), N.ptr(image), N.ptr(alpha), N.ptr(depth),
                               N.ptr(fr.pix_flags), N.ptr(fr.cell_neval), N.ptr(g_image), N.ptr(g_alpha), N.ptr(g_depth), N.ptr(fr.live_bits),
-                              0 if fr.live_bits is None else fr.live_bits.shape[1], N.ptr(pair_grads),
+                              _live_words(fr), N.ptr(pair_grads),
                               N.ptr(slot_live), fr.T, 0, 0)
         if want_abs:
             abs_grads = torch.empty((fr.T * G, 2), dtype=f32, device=dev)
@@ -1247,42 +1286,31 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
             aga.partial_groups, aga.accumulate = ba.cell_count or G, 1 if batch else 0
             N.check(lib.gs_gather_abs_partials(C.byref(aga), s), "gs_gather_abs_partials")
 
+        sums.partials = pair_grads
         if G < cam.groups:
-            batch_sums = torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
-            ga = N.GsProjectBwdArgs()
-            ga.g.n = n
-            ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
-            ga.pair_grads, ga.slot_live, ga.grad_sums = N.ptr(pair_grads), N.ptr(slot_live), N.ptr(batch_sums)
+            ga = sums.gather_args(pair_grads, slot_live)
             for b, c0 in enumerate(range(0, Q, G)):
                 ba.cell_begin, ba.cell_count = c0, min(G, Q - c0)
-                ga.partial_groups = ba.cell_count
                 if b:
                     slot_live.zero_()
                 blend_backward(b)
-                N.check(lib.gs_gather_partials(C.byref(ga), 1 if b else 0, s), "gs_gather_partials")
+                sums.gather(lib, ga, ba.cell_count, s)
         else:
             StageTimer.mark("blend_bwd")
             blend_backward(0)
+            sums.flags = slot_live  # (one batch: left as partials, for the next pass or the projection to sum)
     grads, rows_ready, chunks = _grad_buffers(out, n, cov3d is None, sh_degree, dev)
     d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = grads
     gm = None if g_means2d is None else g_means2d.contiguous()
     gc = None if g_conics is None else g_conics.contiguous()
     gst = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
+    # (the colour pass's sums first, then every feature chunk's and the distortion's added:
+    # one projection backward over the total)
     if feat is not None and fr.M > 0 and fr.T > 0:
-        # (the colour pass's sums first -- gathered here when its one batch left them as
-        # partials -- then every feature chunk's added: one projection backward over the total)
-        colour_sums = batch_sums if (pair_grads is not None and fr.groups < cam.groups) else None
-        grad_sums = _feature_backward(lib, cam, fr, feat, n, pair_grads, slot_live, colour_sums, s)
-        pair_grads = slot_live = None
-    elif pair_grads is not None and fr.groups < cam.groups:
-        grad_sums, pair_grads, slot_live = batch_sums, None, None  # (summed batch by batch above)
-    else:
-        grad_sums = None if pair_grads is None else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
+        _feature_backward(lib, cam, fr, feat, sums, s)
     if dist is not None and fr.M > 0 and fr.T > 0:
-        # (partials not yet gathered go first, into the buffer made for them; sums gathered above are added to)
-        grad_sums = _distortion_backward(lib, cam, fr, dist, n, pair_grads, slot_live,
-                                         grad_sums if pair_grads is None else None, s)
-        pair_grads = slot_live = None
+        _distortion_backward(lib, cam, fr, dist, sums, s)
+    pair_grads, slot_live, grad_sums = sums.for_projection()
     pb = N.GsProjectBwdArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(fr.vis), N.ptr(fr.rects),
                             # Gaussian order (order=NULL): inputs/outputs stream; walking in depth
                             # order coalesces the slot reads but scatters 10 arrays (measured 2.4x slower)
@@ -1498,53 +1526,28 @@ def _feature_forward(cam: CameraParams, fr: _Frame, staged: torch.Tensor, channe
     if fr.M == 0 or fr.T == 0:
         return torch.zeros((channels, H, W), dtype=torch.float32, device=dev)
     out = torch.empty((channels, H, W), dtype=torch.float32, device=dev)
-    fa = N.GsFeatureFwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                            N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
-                            0 if fr.live_bits is None else fr.live_bits.shape[1], fr.T, n, channels,
-                            N.ptr(staged), N.ptr(out))
+    fa = N.GsFeatureFwdArgs(replay_frame(cam, fr, n), channels, N.ptr(staged), N.ptr(out))
     StageTimer.mark("features_fwd")
     N.check(N.load().gs_blend_features_forward(C.byref(fa), _stream()), "gs_blend_features_forward")
     StageTimer.mark("~end_features_fwd")
     return out
 
 
-def _feature_backward(lib, cam: CameraParams, fr: _Frame, feat: _FeaturePass, n: int, pair_grads, slot_live,
-                      colour_sums, s) -> torch.Tensor:
+def _feature_backward(lib, cam: CameraParams, fr: _Frame, feat: _FeaturePass, sums: _GradSums, s) -> None:
     """The feature pass's backward over a stage-path frame: per chunk and cell
     batch (the frame's own plan: fr.groups cells at a time) the blend backward
-    of that chunk and its gather -- geometry sums added to grad_sums, the
-    chunk's columns of feat.d_features stored by a chunk's first batch and
-    added to by the later ones.  Returns grad_sums [n, 10] for the projection
-    backward.  pair_grads / slot_live: the colour pass's one-batch partials,
-    not yet gathered (gathered here first, then the buffer is reused), or
-    None; colour_sums: its sums when it ran in batches, or None.  The flags
-    are this call's own scratch, cleared before every launch."""
-    dev = feat.out.device
-    f32 = torch.float32
-    G, Q, T, Cn = fr.groups, cam.cells, fr.T, feat.channels
-    ga = N.GsProjectBwdArgs()
-    have = colour_sums is not None
-    grad_sums = colour_sums if have else torch.empty((n, N.GS_PAIR_GRAD_FLOATS), dtype=f32, device=dev)
-    if pair_grads is not None and not have:
-        ga.g.n = n
-        ga.vis, ga.rects, ga.pair_offset = N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset)
-        ga.pair_grads, ga.slot_live, ga.grad_sums = N.ptr(pair_grads), N.ptr(slot_live), N.ptr(grad_sums)
-        ga.partial_groups = G
-        N.check(lib.gs_gather_partials(C.byref(ga), 0, s), "gs_gather_partials")
-        have = True
-    if pair_grads is None or pair_grads.shape[0] < T * G:
-        pair_grads = torch.empty((T * G, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
-    flags = torch.empty((T * G,), dtype=torch.uint8, device=dev)
-    g_out = feat.g_out
-    if g_out.dtype != f32 or not g_out.is_contiguous():
-        g_out = g_out.to(f32).contiguous()
-    d_features = torch.empty((n, Cn), dtype=f32, device=dev)
-    ba = N.GsFeatureBwdArgs(cam.to_struct(), cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                            N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(fr.live_bits),
-                            0 if fr.live_bits is None else fr.live_bits.shape[1], T, n, Cn, 0, N.ptr(feat.staged),
-                            N.ptr(feat.out), N.ptr(g_out), N.ptr(pair_grads), N.ptr(flags), 0, 0)
+    of that chunk and its gather -- geometry sums added to `sums`, the chunk's
+    columns of feat.d_features stored by a chunk's first batch and added to by
+    the later ones."""
+    n, f32 = sums.n, torch.float32
+    G, Q, Cn = fr.groups, cam.cells, feat.channels
+    pair_grads, flags = sums.scratch(lib, s)
+    g_out = _fp32_contiguous(feat.g_out)
+    d_features = torch.empty((n, Cn), dtype=f32, device=sums.dev)
+    ba = N.GsFeatureBwdArgs(replay_frame(cam, fr, n), Cn, 0, N.ptr(feat.staged), N.ptr(feat.out), N.ptr(g_out),
+                            N.ptr(pair_grads), N.ptr(flags), 0, 0)
     fg = N.GsFeatureGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(pair_grads),
-                               N.ptr(flags), G, 0, N.ptr(grad_sums), N.ptr(d_features), d_features.stride(0), 0, 0, 0)
+                               N.ptr(flags), G, 0, N.ptr(sums.sums), N.ptr(d_features), d_features.stride(0), 0, 0, 0)
     StageTimer.mark("features_bwd")
     for chunk in range(_feature_chunks(Cn)):
         ba.chunk = chunk
@@ -1553,63 +1556,79 @@ def _feature_backward(lib, cam: CameraParams, fr: _Frame, feat: _FeaturePass, n:
         for b, c0 in enumerate(range(0, Q, G)):
             ba.cell_begin, ba.cell_count = c0, min(G, Q - c0)
             fg.partial_groups = ba.cell_count
-            fg.accumulate, fg.feature_accumulate = (1 if have else 0), (1 if b else 0)
+            fg.accumulate, fg.feature_accumulate = sums.accumulate(), (1 if b else 0)
             flags.zero_()
             N.check(lib.gs_blend_features_backward(C.byref(ba), s), "gs_blend_features_backward")
             N.check(lib.gs_gather_feature_partials(C.byref(fg), s), "gs_gather_feature_partials")
-            have = True
     StageTimer.mark("~end_features_bwd")
     feat.d_features = d_features
-    return grad_sums
 
 
-class RasterizeGaussianFeatures(torch.autograd.Function):
-    """RasterizeGaussians with one more differentiable input, features [N, C],
-    and one more output, the feature image [C, H, W] composited with the
-    colour pass's own weights.  The frame is the stage path's (the feature
-    kernels read its buffers); the seven other outputs, and their gradients
-    when the feature image takes no part in the loss, are RasterizeGaussians'
-    bit for bit."""
+class RasterizeGaussians(torch.autograd.Function):
+    """Differentiable render: inputs are the model accessors' tensors, outputs
+    are (image, alpha, depth, viewspace_points, conics, radii, visibility),
+    then the feature image [C, H, W] when `features` [N, C] were given (one
+    more differentiable input, composited with the colour pass's own weights),
+    then the distortion map when `distort` asks for it."""
 
     @staticmethod
-    def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None,
-                distort=None):
-        # distort: a _DistortionPass: a ninth output, the distortion map, follows the feature image
+    def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, view, cam: CameraParams,
+                opacity_is_logit=False, sh_degree=0, grad_dest=None, density_stats=None, contrib=None, distort=None):
+        # features, contrib (a _ContributionPass), distort (a _DistortionPass), density_stats with
+        # abs_accum (its backward is gs_blend_backward_abs): the frame is then the stage path's, whose
+        # buffers the replays read -- the seven standard outputs and their gradients are the same bits;
+        # the contribution pass runs at the end of this forward
+        # density_stats: a DensityStats this frame's backward adds the view to (it needs the
+        # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape)
+        # view: None, or the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
+        # Gaussians' device, given only to receive its gradient -- the forward
+        # reads the pose from `cam`, whose values are the same
         image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
             cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
-            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]), stage_path=True)
-        ctx.density = None if density_stats is None else (density_stats, radii)
-        n, channels = int(features.shape[0]), int(features.shape[1])
-        staged = _stage_features(features)
-        feat_image = _feature_forward(cam, fr, staged, channels, n, xyz.device)
-        dist_out = () if distort is None else (_distortion_forward(cam, fr, n, distort, xyz.device),)
+            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]),
+            stage_path=features is not None or contrib is not None or distort is not None or
+            (density_stats is not None and density_stats.abs_accum is not None))
+        n, dev = int(xyz.shape[0]), xyz.device
+        extra = ()
+        ctx.feature_shape = None if features is None else (n, int(features.shape[1]))
+        if features is not None:
+            staged = _stage_features(features)
+            extra = (staged, _feature_forward(cam, fr, staged, ctx.feature_shape[1], n, dev))
+        if distort is not None:
+            extra += (_distortion_forward(cam, fr, n, distort, dev),)
         if contrib is not None:
-            _contribution_pass(cam, fr, n, contrib, xyz.device)
+            _contribution_pass(cam, fr, n, contrib, dev)
         ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
         ctx.grad_dest = grad_dest
-        ctx.feature_shape = (n, channels)
         ctx.distort = distort
-        ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[12] else None
+        ctx.density = None if density_stats is None else (density_stats, radii)
+        ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[8] else None
+        # (the outputs image / alpha / depth too: the blend backward's per-pixel
+        # state; autograd refuses the backward if they were modified in place)
         ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
-                              depth, staged, feat_image, *dist_out)
+                              depth, *extra)
         ctx.mark_non_differentiable(radii, vis)
         ctx.set_materialize_grads(False)
-        return (image, alpha, depth, means2d, conics, radii, vis, feat_image) + dist_out
+        return (image, alpha, depth, means2d, conics, radii, vis) + extra[1 if features is not None else 0:]
 
     @staticmethod
-    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, g_features, *g_dist):
-        (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth, staged,
-         feat_image, *dist_out) = ctx.saved_tensors
-        # (no cotangent on the distortion map: no launch for it)
-        dist = _DistortionGrad(ctx.distort, dist_out[0], g_dist[0]) if g_dist and g_dist[0] is not None else None
+    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, *g_extra):
+        (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth,
+         *extra) = ctx.saved_tensors
+        g_extra = list(g_extra)
+        # (no cotangent on the feature image or the distortion map: no launch for it)
+        feat = dist = None
+        if ctx.feature_shape is not None:
+            staged, feat_image, g_features = extra[0], extra[1], g_extra.pop(0)
+            if g_features is not None:
+                feat = _FeaturePass(staged, feat_image, g_features, ctx.feature_shape[1])
+        if ctx.distort is not None and g_extra[0] is not None:
+            dist = _DistortionGrad(ctx.distort, extra[-1], g_extra[0])
         g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
         dest = ctx.grad_dest() if ctx.grad_dest is not None else None
         d_view = None
         if ctx.view_shape is not None:
             d_view = torch.empty((12,), dtype=torch.float32, device=xyz.device)
-        # (no cotangent on the feature image: RasterizeGaussians' backward, launch for launch)
-        feat = None if g_features is None else _FeaturePass(staged, feat_image, g_features, ctx.feature_shape[1])
         d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
             ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
             g_image, g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
@@ -1633,77 +1652,7 @@ class RasterizeGaussianFeatures(torch.autograd.Function):
                 d_col.view(logits.shape) if need[4] else None,
                 d_op.view(opacity.shape) if need[5] else None,
                 d_sh if (sh_rest is not None and need[6]) else None,
-                d_features, None, None, None, None, g_view, None, None, None)
-
-
-class RasterizeGaussians(torch.autograd.Function):
-    """Differentiable render: inputs are the model accessors' tensors, outputs
-    are (image, alpha, depth, viewspace_points, conics, radii, visibility)."""
-
-    @staticmethod
-    def forward(ctx, xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam: CameraParams,
-                opacity_is_logit=False, sh_degree=0, grad_dest=None, view=None, density_stats=None, contrib=None,
-                distort=None):
-        # contrib: a _ContributionPass: the frame is then the stage path's (the same bits) and the
-        # contribution pass runs at the end of this forward
-        # distort: a _DistortionPass: the stage path too, and an eighth output, the distortion map
-        # density_stats: a DensityStats this frame's backward adds the view to (it needs the
-        # forward's radii, kept on ctx: a non-differentiable output, no cycle through the tape);
-        # with abs_accum the stage path too: its backward is gs_blend_backward_abs
-        # view: the camera's W2C rows as an fp32 [3,4] / [4,4] tensor on the
-        # Gaussians' device, given only to receive its gradient -- the forward
-        # reads the pose from `cam`, whose values are the same
-        image, alpha, depth, means2d, conics, radii, vis, fr = forward_pipeline(
-            cam, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree,
-            need_grad=_FUSE_FLAGS and any(ctx.needs_input_grad[:7]),
-            stage_path=contrib is not None or distort is not None or
-            (density_stats is not None and density_stats.abs_accum is not None))
-        dist_out = () if distort is None else (_distortion_forward(cam, fr, int(xyz.shape[0]), distort, xyz.device),)
-        if contrib is not None:
-            _contribution_pass(cam, fr, int(xyz.shape[0]), contrib, xyz.device)
-        ctx.cam, ctx.frame, ctx.opacity_is_logit, ctx.sh_degree = cam, fr, opacity_is_logit, sh_degree
-        ctx.grad_dest = grad_dest
-        ctx.distort = distort
-        ctx.density = None if density_stats is None else (density_stats, radii)
-        ctx.view_shape = tuple(view.shape) if view is not None and ctx.needs_input_grad[11] else None
-        # (the outputs image / alpha / depth too: the blend backward's per-pixel
-        # state; autograd refuses the backward if they were modified in place)
-        ctx.save_for_backward(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha,
-                              depth, *dist_out)
-        ctx.mark_non_differentiable(radii, vis)
-        ctx.set_materialize_grads(False)
-        return (image, alpha, depth, means2d, conics, radii, vis) + dist_out
-
-    @staticmethod
-    def backward(ctx, g_image, g_alpha, g_depth, g_means2d, g_conics, _g_radii, _g_vis, *g_dist):
-        (xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, means2d, conics, image, alpha, depth,
-         *dist_out) = ctx.saved_tensors
-        # (no cotangent on the distortion map: no launch for it)
-        dist = _DistortionGrad(ctx.distort, dist_out[0], g_dist[0]) if g_dist and g_dist[0] is not None else None
-        g_conics = None if g_conics is None else g_conics.reshape(-1, 4)
-        dest = ctx.grad_dest() if ctx.grad_dest is not None else None
-        d_view = None
-        if ctx.view_shape is not None:
-            d_view = torch.empty((12,), dtype=torch.float32, device=xyz.device)
-        d_xyz, d_cov, d_scl, d_rot, d_col, d_op, d_sh = backward_pipeline(
-            ctx.cam, ctx.frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics,
-            g_image, None if g_alpha is None else g_alpha, g_depth, g_means2d, g_conics, ctx.opacity_is_logit,
-            sh_rest, ctx.sh_degree, out=dest, outputs=(image, alpha, depth), d_view=d_view, density=ctx.density,
-            dist=dist)
-        need = ctx.needs_input_grad
-        g_view = None
-        if d_view is not None:
-            g_view = d_view.view(3, 4)
-            if ctx.view_shape == (4, 4):
-                g_view = torch.cat([g_view, g_view.new_zeros((1, 4))], 0)
-        return (d_xyz if need[0] else None,
-                d_cov if (cov3d is not None and need[1]) else None,
-                d_scl if (scaling is not None and need[2]) else None,
-                d_rot if (rotation is not None and need[3]) else None,
-                d_col.view(logits.shape) if need[4] else None,
-                d_op.view(opacity.shape) if need[5] else None,
-                d_sh if (sh_rest is not None and need[6]) else None,
-                None, None, None, None, g_view, None, None, None)
+                d_features, g_view, None, None, None, None, None, None, None)
 
 
 def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit=False,
@@ -1820,29 +1769,18 @@ def rasterize(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opacity,
     xyz, _ = _rows(xyz, 3)
     logits, _ = _rows(logits, 3)
     opacity, _ = _rows(opacity, 1)
-    # (the statistics ride behind `view`, only when given: without them the calls are the ones they were)
-    stats = () if density_stats is None else (density_stats,)
     cp = _ContributionPass(contribution_stats, dominant) if (contribution_stats is not None or dominant) else None
-    if cp is not None:
-        stats = (density_stats, cp)
-    if dp is not None:
-        stats = (density_stats, cp, dp)
     if view is None or not (isinstance(view, torch.Tensor) and view.requires_grad):
-        if stats:
-            stats = (None,) + stats
+        view = None
     else:
         if not view.is_floating_point() or tuple(view.shape) not in ((3, 4), (4, 4)):
             raise ValueError(f"view must be a floating-point [3,4] or [4,4] tensor, got {view.dtype} "
                              f"{tuple(view.shape)}")
         # (differentiable, as the reference's .to(device): the gradient returns to
         # the caller's device and dtype)
-        stats = (view.to(device=xyz.device, dtype=torch.float32),) + stats
-    if features is not None:
-        outs = RasterizeGaussianFeatures.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features,
-                                               cam, bool(opacity_is_logit), sh_degree, grad_dest, *stats)
-    else:
-        outs = RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, cam,
-                                        bool(opacity_is_logit), sh_degree, grad_dest, *stats)
+        view = view.to(device=xyz.device, dtype=torch.float32)
+    outs = RasterizeGaussians.apply(xyz, cov3d, scaling, rotation, logits, opacity, sh_rest, features, view, cam,
+                                    bool(opacity_is_logit), sh_degree, grad_dest, density_stats, cp, dp)
     if dp is not None:
         outs = tuple(outs) + (dp.median_depth, dp.median_id)
     if cp is not None and cp.dominant:

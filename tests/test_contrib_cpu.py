@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import replay_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -54,6 +56,8 @@ def test_struct_layouts_match_c(pkg, tmp_path):
         exp.extend(getattr(mirror, field).offset for field, _ in mirror._fields_)
     exp.append(N.GS_CONTRIB_STRIDE)
     assert got == exp
+    # the frame inside gs_contrib_args, field by field, and the bytes the flat struct had
+    replay_layout.check(pkg, tmp_path, ["gs_contrib_args"])
 
 
 # --------------------------------------------------------- 2: validation ----

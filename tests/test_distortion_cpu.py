@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import distortion_util as DU
+import replay_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -89,6 +90,8 @@ def test_struct_layouts_match_c(pkg, tmp_path):
         want.append(C.sizeof(t))
         want += [getattr(t, fname).offset for fname, *_ in t._fields_]
     assert got == want
+    # the frame inside both structs, field by field, and the bytes the flat structs had
+    replay_layout.check(pkg, tmp_path, ["gs_distortion_fwd_args", "gs_distortion_bwd_args"])
     assert "gs_blend_distortion_forward" in N.EXPORTS and "gs_blend_distortion_backward" in N.EXPORTS
     assert N.GS_ABI_VERSION == 23
 

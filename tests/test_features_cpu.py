@@ -5,6 +5,8 @@ import ctypes as C
 import os
 import subprocess
 
+import replay_layout
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -30,6 +32,8 @@ def test_feature_struct_layouts_match_c(pkg, tmp_path):
     got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
     assert got == [C.sizeof(N.GsFeatureFwdArgs), C.sizeof(N.GsFeatureBwdArgs), C.sizeof(N.GsFeatureGatherArgs),
                    N.GS_FEATURE_CHUNK, N.GS_MAX_FEATURE_CHANNELS]
+    # every offset of the two structs that begin with the frame, and the bytes the flat structs had
+    replay_layout.check(pkg, tmp_path, ["gs_feature_fwd_args", "gs_feature_bwd_args"])
 
 
 def test_forward_rejects_bad_arguments(pkg):

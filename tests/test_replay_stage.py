@@ -501,8 +501,9 @@ def _gpu(pkg, cuda, name):
 
 
 def _replay_args(N, r, live):
-    return (r.cam.to_struct(), r.cam.tiles_x, r.cam.tiles_y, N.ptr(r.ranges), N.ptr(r.sorted_gauss), N.ptr(r.records),
-            N.ptr(r.fwd["cell_neval"]), N.ptr(r.fwd["live"]) if live else None, r.live_words if live else 0, r.T, r.n)
+    return N.GsReplayFrame(r.cam.to_struct(), r.cam.tiles_x, r.cam.tiles_y, N.ptr(r.ranges), N.ptr(r.sorted_gauss),
+                           N.ptr(r.records), N.ptr(r.fwd["cell_neval"]), N.ptr(r.fwd["live"]) if live else None,
+                           r.live_words if live else 0, r.T, r.n)
 
 
 def _run(pkg, fn, args):
@@ -533,7 +534,8 @@ def feat_forward(pkg, r, F, live=True):
     staged = pkg.rasterizer._stage_features(torch.from_numpy(np.ascontiguousarray(F)).to(dev))
     assert staged.shape == (R.chunks_of(Cn), r.n, 4)
     out = Guarded((Cn, r.fr.H, r.fr.W), dev)
-    _run(pkg, "gs_blend_features_forward", N.GsFeatureFwdArgs(*_replay_args(N, r, live), Cn, N.ptr(staged), N.ptr(out.t)))
+    _run(pkg, "gs_blend_features_forward",
+         N.GsFeatureFwdArgs(_replay_args(N, r, live), Cn, N.ptr(staged), N.ptr(out.t)))
     assert out.intact(), "written past the feature image"
     return staged, out
 
@@ -541,7 +543,7 @@ def feat_forward(pkg, r, F, live=True):
 def feat_backward(pkg, r, staged, out, g_out, Cn, chunk, live=True, begin=0, count=0):
     N = pkg._native
     grads, flags = _scratch(r, count, N.GS_PARTIAL_STRIDE, r.records.device)
-    a = N.GsFeatureBwdArgs(*_replay_args(N, r, live), Cn, chunk, N.ptr(staged), N.ptr(out.t), N.ptr(g_out.t),
+    a = N.GsFeatureBwdArgs(_replay_args(N, r, live), Cn, chunk, N.ptr(staged), N.ptr(out.t), N.ptr(g_out.t),
                            N.ptr(grads.t), N.ptr(flags.t), begin, count)
     _run(pkg, "gs_blend_features_backward", a)
     assert grads.intact() and flags.intact() and g_out.intact() and out.intact()
@@ -779,7 +781,7 @@ def contributions(pkg, r, live=True, begin=0, count=0, dominant=True):
     part, flags = _scratch(r, count, N.GS_CONTRIB_STRIDE, dev)
     did = Guarded((r.fr.H * r.fr.W,), dev, torch.int32, fill=-7, guard_fill=9)
     dw = Guarded((r.fr.H * r.fr.W,), dev)
-    a = N.GsContribArgs(*_replay_args(N, r, live), N.ptr(part.t), N.ptr(flags.t), begin, count,
+    a = N.GsContribArgs(_replay_args(N, r, live), N.ptr(part.t), N.ptr(flags.t), begin, count,
                         N.ptr(did.t) if dominant else None, N.ptr(dw.t) if dominant else None)
     _run(pkg, "gs_blend_contributions", a)
     assert part.intact() and flags.intact() and did.intact() and dw.intact()
@@ -942,7 +944,7 @@ def dist_forward(pkg, r, nf, live=True):
     H, W = r.fr.H, r.fr.W
     o = dict(D=Guarded((H * W,), dev), moments=Guarded((2, H * W), dev), median_depth=Guarded((H * W,), dev),
              median_id=Guarded((H * W,), dev, torch.int32, fill=-7, guard_fill=9))
-    a = N.GsDistortionFwdArgs(*_replay_args(N, r, live), *_nf(nf), N.ptr(o["D"].t), N.ptr(o["moments"].t),
+    a = N.GsDistortionFwdArgs(_replay_args(N, r, live), *_nf(nf), N.ptr(o["D"].t), N.ptr(o["moments"].t),
                               N.ptr(o["median_depth"].t), N.ptr(o["median_id"].t))
     _run(pkg, "gs_blend_distortion_forward", a)
     assert all(v.intact() for v in o.values())
@@ -952,7 +954,7 @@ def dist_forward(pkg, r, nf, live=True):
 def dist_backward(pkg, r, nf, fwd, g_out, live=True, begin=0, count=0):
     N = pkg._native
     grads, flags = _scratch(r, count, N.GS_PARTIAL_STRIDE, r.records.device)
-    a = N.GsDistortionBwdArgs(*_replay_args(N, r, live), *_nf(nf), N.ptr(fwd["D"].t), N.ptr(fwd["moments"].t),
+    a = N.GsDistortionBwdArgs(_replay_args(N, r, live), *_nf(nf), N.ptr(fwd["D"].t), N.ptr(fwd["moments"].t),
                               N.ptr(g_out.t), N.ptr(grads.t), N.ptr(flags.t), begin, count)
     _run(pkg, "gs_blend_distortion_backward", a)
     assert grads.intact() and flags.intact() and g_out.intact()

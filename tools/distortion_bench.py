@@ -74,7 +74,7 @@ def run(config="C3", reps=20, seed=0, near_far=(0.1, 1000.0)):
     s = N.stream_ptr()
     f32 = torch.float32
     frame = (cs, camp.tiles_x, camp.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss), N.ptr(fr.records))
-    replay = frame + (N.ptr(fr.cell_neval), N.ptr(live), lw, T, n)
+    replay = RZ.replay_frame(camp, fr, n)
 
     # the colour pass, the forward into scratch copies of everything it writes
     scratch = [torch.empty_like(t) for t in (image, alpha, depth, fr.pix_flags, fr.cell_neval)]
@@ -96,8 +96,8 @@ def run(config="C3", reps=20, seed=0, near_far=(0.1, 1000.0)):
     fimg = torch.empty((4, H, W), dtype=f32, device=dev)
     gF = (torch.rand((4, H, W), generator=g) * 2 - 1).to(dev)
     dF = torch.empty((n, 4), dtype=f32, device=dev)
-    ff = N.GsFeatureFwdArgs(*replay, 4, N.ptr(stagedF), N.ptr(fimg))
-    fb = N.GsFeatureBwdArgs(*replay, 4, 0, N.ptr(stagedF), N.ptr(fimg), N.ptr(gF), N.ptr(pg), N.ptr(flags), 0, 0)
+    ff = N.GsFeatureFwdArgs(replay, 4, N.ptr(stagedF), N.ptr(fimg))
+    fb = N.GsFeatureBwdArgs(replay, 4, 0, N.ptr(stagedF), N.ptr(fimg), N.ptr(gF), N.ptr(pg), N.ptr(flags), 0, 0)
     fg = N.GsFeatureGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(pg), N.ptr(flags),
                                G, 1, N.ptr(sums), N.ptr(dF), dF.stride(0), 0, 4, 0)
 
@@ -107,8 +107,8 @@ def run(config="C3", reps=20, seed=0, near_far=(0.1, 1000.0)):
     medz = torch.empty((H, W), dtype=f32, device=dev)
     medi = torch.empty((H, W), dtype=torch.int32, device=dev)
     gD = (torch.rand((H, W), generator=g) * 2 - 1).to(dev)
-    df = N.GsDistortionFwdArgs(*replay, 0.0, 0.0, N.ptr(dist), N.ptr(mom), N.ptr(medz), N.ptr(medi))
-    db = N.GsDistortionBwdArgs(*replay, 0.0, 0.0, N.ptr(dist), N.ptr(mom), N.ptr(gD), N.ptr(pg), N.ptr(flags), 0, 0)
+    df = N.GsDistortionFwdArgs(replay, 0.0, 0.0, N.ptr(dist), N.ptr(mom), N.ptr(medz), N.ptr(medi))
+    db = N.GsDistortionBwdArgs(replay, 0.0, 0.0, N.ptr(dist), N.ptr(mom), N.ptr(gD), N.ptr(pg), N.ptr(flags), 0, 0)
 
     def call(fn, args, what, *extra):
         return lambda: N.check(fn(C.byref(args), *extra, s), what)

@@ -109,12 +109,9 @@ def run(config="C3", reps=20, channels=(4, 16), seed=0):
         fimg = torch.empty((c, H, W), dtype=f32, device=dev)
         gF = (torch.rand((c, H, W), generator=g) * 2 - 1).to(dev)
         dF = torch.empty((n, c), dtype=f32, device=dev)
-        ff = N.GsFeatureFwdArgs(cs, camp.tiles_x, camp.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                                N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(live), lw, T, n, c, N.ptr(staged),
-                                N.ptr(fimg))
-        fb = N.GsFeatureBwdArgs(cs, camp.tiles_x, camp.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
-                                N.ptr(fr.records), N.ptr(fr.cell_neval), N.ptr(live), lw, T, n, c, 0, N.ptr(staged),
-                                N.ptr(fimg), N.ptr(gF), N.ptr(pg), N.ptr(flags), 0, 0)
+        replay = RZ.replay_frame(camp, fr, n)
+        ff = N.GsFeatureFwdArgs(replay, c, N.ptr(staged), N.ptr(fimg))
+        fb = N.GsFeatureBwdArgs(replay, c, 0, N.ptr(staged), N.ptr(fimg), N.ptr(gF), N.ptr(pg), N.ptr(flags), 0, 0)
         fg = N.GsFeatureGatherArgs(n, N.ptr(fr.vis), N.ptr(fr.rects), N.ptr(fr.pair_offset), N.ptr(pg), N.ptr(flags),
                                    G, 1, N.ptr(sums), N.ptr(dF), dF.stride(0), 0, 0, 0)
         chunks = (c + N.GS_FEATURE_CHUNK - 1) // N.GS_FEATURE_CHUNK
