@@ -20,7 +20,8 @@ SRC = [os.path.join(HERE, "csrc", n) for n in (
     "gs_loss.hip", "gs_densify.hip", "gs_mcmc.hip", "gs_filter3d.hip", "gs_normals.hip", "gs_bilagrid.hip",
     "gs_tsdf.hip", "gs_render.hip")]
 HDR = [os.path.join(ROOT, "include", "gsplat_mi355x.h"), os.path.join(HERE, "csrc", "gs_internal.h"),
-       os.path.join(HERE, "csrc", "gs_device.h"), os.path.join(HERE, "csrc", "gs_blend_device.h")]
+       os.path.join(HERE, "csrc", "gs_device.h"), os.path.join(HERE, "csrc", "gs_blend_device.h"),
+       os.path.join(HERE, "csrc", "gs_gather_device.h")]
 OUT = os.path.join(HERE, "libgsplat_mi355x.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

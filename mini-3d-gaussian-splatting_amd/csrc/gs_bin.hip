@@ -55,8 +55,7 @@ __global__ __launch_bounds__(kBlock) void k_bin_partials(gs_bin_args a, uint32_t
   for (int i = 0; i < kR; ++i) {
     const long long k = base + i * kBlock + threadIdx.x;
     if (k < a.n) {
-      sum += rect_touches((int)(rc_d[i].x & 0xFFFFu), (int)(rc_d[i].x >> 16), (int)(rc_d[i].y & 0xFFFFu),
-                          (int)(rc_d[i].y >> 16));
+      sum += rect_touches(rc_d[i]);
       nvis += vis_o[i] ? 1u : 0u;
     }
   }
@@ -68,9 +67,7 @@ __global__ __launch_bounds__(kBlock) void k_bin_partials(gs_bin_args a, uint32_t
 #pragma unroll
   for (int i = 0; i < kR; ++i) {
     const long long g = base + i * kBlock + threadIdx.x;
-    cnt[i] = g < a.n ? rect_touches((int)(rc_own[i].x & 0xFFFFu), (int)(rc_own[i].x >> 16),
-                                    (int)(rc_own[i].y & 0xFFFFu), (int)(rc_own[i].y >> 16))
-                     : 0u;
+    cnt[i] = g < a.n ? rect_touches(rc_own[i]) : 0u;
   }
   // the block's touches (depth order) and visible count, and round 0's slot
   // prefix, in one scan
@@ -305,8 +302,7 @@ __global__ __launch_bounds__(kBlock) void k_bin_emit(gs_bin_args a, const uint32
   for (int r = 0; r < kR; ++r) {
     const long long k = base + r * kBlock + threadIdx.x;
     if (k < a.n) {
-      cntr[r] = rect_touches((int)(rcr[r].x & 0xFFFFu), (int)(rcr[r].x >> 16), (int)(rcr[r].y & 0xFFFFu),
-                             (int)(rcr[r].y >> 16));
+      cntr[r] = rect_touches(rcr[r]);
     } else {
       cntr[r] = 0u;
       gr[r] = 0xFFFFFFFFu;

@@ -1,6 +1,7 @@
 // gs_device.h -- what more than one stage of the render path uses: the block
-// geometry, the block scans, the DPP lane sums (oct_sum, and lanes_sum of the
-// gathers), the under-aligned vector types, the counter-based normals, the
+// geometry, the block scans, the packed tile rectangle, the DPP lane sums
+// (oct_sum, and lanes_sum / lanes_max of the gathers, whose walk is
+// gs_gather_device.h), the under-aligned vector types, the counter-based normals, the
 // one Adam update, and the host-side camera check.  Everything is in an
 // anonymous namespace (each .hip file is its own translation unit and code
 // object); a helper with a single user lives in that user's file, and what
@@ -98,6 +99,9 @@ __device__ __forceinline__ uint3 block_exscan3(uint3 v, uint32_t (*s_tmp)[kBlock
 __device__ __forceinline__ uint32_t rect_touches(int tx0, int tx1, int ty0, int ty1) {
   return (tx1 >= tx0 && ty1 >= ty0) ? (uint32_t)((tx1 - tx0 + 1) * (ty1 - ty0 + 1)) : 0u;
 }
+__device__ __forceinline__ uint32_t rect_touches(uint2 r) {  // (tx0 | tx1 << 16, ty0 | ty1 << 16)
+  return rect_touches((int)(r.x & 0xFFFFu), (int)(r.x >> 16), (int)(r.y & 0xFFFFu), (int)(r.y >> 16));
+}
 
 // ------------------------------------------------- counter-based noise ----
 // splitmix64's finaliser: the hash every seeded draw here goes through
@@ -152,6 +156,21 @@ __device__ __forceinline__ float lanes_sum(float v) {
     asm volatile("" : "+v"(v));
     return v;
   }
+  return v;
+}
+// the same steps over integers, and over fmaxf
+template <int LPG>
+__device__ __forceinline__ int lanes_sum(int v) {
+  if constexpr (LPG >= 2) v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+  if constexpr (LPG >= 4) v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+  if constexpr (LPG == 8) v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+  return v;
+}
+template <int LPG>
+__device__ __forceinline__ float lanes_max(float v) {
+  if constexpr (LPG >= 2) v = fmaxf(v, dpp_row<0xB1>(v));
+  if constexpr (LPG >= 4) v = fmaxf(v, dpp_row<0x4E>(v));
+  if constexpr (LPG == 8) v = fmaxf(v, dpp_row<0x141>(v));
   return v;
 }
 

@@ -23,6 +23,7 @@
 #include "gs_internal.h"
 #include "gs_device.h"
 #include "gs_blend_device.h"
+#include "gs_gather_device.h"
 
 namespace {
 
@@ -427,41 +428,23 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 6))) v
 }
 
 // ========================================================== gather ========
-// k_gather_slots' walk (gs_project.hip): QL x HL lanes per Gaussian, lane
-// (h, q) adds the live partials of g's slots h, h + HL, ... for the partial
-// groups q, q + QL, ..., then the lane sums are added in the same DPP order.
+// slot_walk (gs_gather_device.h) over a chunk's 40-B partials, a slot at a
+// time: k_gather_slots' sums, stored as the chunk's.
 template <int QL, int HL>
 __global__ __launch_bounds__(kBlock) void k_gather_feat(gs_feature_gather_args a) {
   constexpr int LPG = QL * HL;
   const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
   const int g = (int)(t / LPG);
-  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
+  const SlotLists s = slot_lists(a);
+  const SlotLane l = slot_lane<QL, HL>(s, t, g);
   float acc[GS_PAIR_GRAD_FLOATS];
 #pragma unroll
   for (int k = 0; k < GS_PAIR_GRAD_FLOATS; ++k) acc[k] = 0.f;
-  const bool valid = g < a.n;
-  const uint32_t gi = valid ? (uint32_t)g : 0u;
-  const uint2 rect = reinterpret_cast<const uint2 *>(a.rects)[gi];
-  const int tx0 = (int)(rect.x & 0xFFFFu), tx1 = (int)(rect.x >> 16);
-  const int ty0 = (int)(rect.y & 0xFFFFu), ty1 = (int)(rect.y >> 16);
-  const size_t off = a.pair_offset[gi];
-  const uint32_t cnt = (valid && a.vis[gi]) ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
-  const uint32_t ng = (uint32_t)a.partial_groups;
-  for (uint32_t qc = (uint32_t)q; qc < ng; qc += QL) {
-    for (uint32_t e = (uint32_t)h; e < cnt; e += HL) {
-      const size_t at = (off + e) * ng + qc;
-      if (!a.slot_live[at]) continue;
-      const float *src = a.pair_grads + at * GS_PARTIAL_STRIDE;
-      const f4_u8 va = *reinterpret_cast<const f4_u8 *>(src), vb = *reinterpret_cast<const f4_u8 *>(src + 4);
-      const f2_u8 vc = *reinterpret_cast<const f2_u8 *>(src + 8);
-      acc[0] += va.x; acc[1] += va.y; acc[2] += va.z; acc[3] += va.w;
-      acc[4] += vb.x; acc[5] += vb.y; acc[6] += vb.z; acc[7] += vb.w;
-      acc[8] += vc.x; acc[9] += vc.y;
-    }
-  }
+  slot_walk<QL, HL, 1, kLoadLazy>(
+      s, l, [&](size_t i) { return load_partial10(a.pair_grads, i); }, [&](const Partial10 &v) { add_partial10(acc, v); });
 #pragma unroll
   for (int k = 0; k < GS_PAIR_GRAD_FLOATS; ++k) acc[k] = lanes_sum<LPG>(acc[k]);
-  if ((t % LPG) != 0 || !valid) return;
+  if ((t % LPG) != 0 || !l.valid) return;
   float *gs = a.grad_sums + (size_t)g * GS_PAIR_GRAD_FLOATS;
   if (a.accumulate) {
 #pragma unroll
@@ -487,13 +470,6 @@ __global__ __launch_bounds__(kBlock) void k_gather_feat(gs_feature_gather_args a
 //    8j..8j+7 reduce entry j's 64 pixels -- lane 8j + x takes column x, rows
 //    0..7 in order -- to (sum, max, count) and finish with 3 DPP steps each.
 constexpr int kCtbRow = kWave + 8;  // rows padded to 72 floats: the 8 entries' columns fall in 64 different banks
-
-__device__ __forceinline__ float oct_max(float v) {
-  v = fmaxf(v, dpp_row<0xB1>(v));
-  v = fmaxf(v, dpp_row<0x4E>(v));
-  v = fmaxf(v, dpp_row<0x141>(v));
-  return v;
-}
 
 __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
   __shared__ float s_c[kBwdGroup][kCtbRow];  // per group entry and pixel: c
@@ -527,7 +503,7 @@ __global__ __launch_bounds__(kWave) void k_contrib(gs_contrib_args a) {
               cnt += c > 0.f ? 1.f : 0.f;
             }
             sum = oct_sum(sum);
-            mx = oct_max(mx);
+            mx = lanes_max<8>(mx);
             cnt = oct_sum(cnt);  // (small integers: exact)
             if (col == 0) {
               const uint32_t slot = Rec2::slot(s_wrec + 2 * j);
@@ -554,50 +530,28 @@ __global__ __launch_bounds__(kBlock) void k_contrib_empty(int32_t *id, float *we
   }
 }
 
-template <int LPG>
-__device__ __forceinline__ float lanes_max(float v) {
-  if constexpr (LPG == 8) return oct_max(v);
-  if constexpr (LPG == 4 || LPG == 2) {
-    v = fmaxf(v, dpp_row<0xB1>(v));
-    if constexpr (LPG == 4) v = fmaxf(v, dpp_row<0x4E>(v));
-  }
-  return v;
-}
-
-// k_gather_feat's walk and lane tree over the 16-byte contribution partials
+// slot_walk (gs_gather_device.h) over the 16-byte contribution partials, a
+// slot at a time; the lane tree of the sums, over max and over integers
 template <int QL, int HL>
 __global__ __launch_bounds__(kBlock) void k_contrib_gather(gs_contrib_gather_args a) {
   constexpr int LPG = QL * HL;
   const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
   const int g = (int)(t / LPG);
-  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
-  const bool valid = g < a.n;
-  const uint32_t gi = valid ? (uint32_t)g : 0u;
-  const bool seen = valid && a.vis[gi];
-  const uint2 rect = reinterpret_cast<const uint2 *>(a.rects)[gi];
-  const int tx0 = (int)(rect.x & 0xFFFFu), tx1 = (int)(rect.x >> 16);
-  const int ty0 = (int)(rect.y & 0xFFFFu), ty1 = (int)(rect.y >> 16);
-  const size_t off = a.pair_offset[gi];
-  const uint32_t cnt = seen ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
-  const uint32_t ng = (uint32_t)a.partial_groups;
+  const SlotLists sl = slot_lists(a);
+  const SlotLane l = slot_lane<QL, HL>(sl, t, g);
   float s = 0.f, m = 0.f;
   int ki = 0;  // (counts as integers: a Gaussian's total may pass 2^24)
-  for (uint32_t qc = (uint32_t)q; qc < ng; qc += QL) {
-    for (uint32_t e = (uint32_t)h; e < cnt; e += HL) {
-      const size_t at = (off + e) * ng + qc;
-      if (!a.slot_live[at]) continue;
-      const float4 v = reinterpret_cast<const float4 *>(a.partials)[at];
-      s += v.x;
-      m = fmaxf(m, v.y);
-      ki += (int)v.z;
-    }
-  }
+  slot_walk<QL, HL, 1, kLoadLazy>(
+      sl, l, [&](size_t i) { return reinterpret_cast<const float4 *>(a.partials)[i]; },
+      [&](const float4 &v) {
+        s += v.x;
+        m = fmaxf(m, v.y);
+        ki += (int)v.z;
+      });
   s = lanes_sum<LPG>(s);
   m = lanes_max<LPG>(m);
-  ki += __builtin_amdgcn_update_dpp(0, ki, 0xB1, 0xF, 0xF, true);
-  if constexpr (LPG >= 4) ki += __builtin_amdgcn_update_dpp(0, ki, 0x4E, 0xF, 0xF, true);
-  if constexpr (LPG == 8) ki += __builtin_amdgcn_update_dpp(0, ki, 0x141, 0xF, 0xF, true);
-  if ((t % LPG) != 0 || !seen) return;
+  ki = lanes_sum<LPG>(ki);
+  if ((t % LPG) != 0 || !l.seen) return;
   a.weight_sum[g] = a.weight_sum[g] + s;
   a.weight_max[g] = fmaxf(a.weight_max[g], m);
   a.pixels[g] += (int64_t)ki;
@@ -826,23 +780,16 @@ gs_status gs_gather_feature_partials(const gs_feature_gather_args *a, gs_stream_
   const char *me = "gs_gather_feature_partials";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
   if (a->n < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative n", me);
-  if (!a->vis || !a->rects || !a->pair_offset || !a->pair_grads || !a->slot_live || !a->grad_sums || !a->d_features)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->partial_groups < 1) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: partial_groups < 1", me);
+  if (const gs_status st = slot_lists_check(slot_lists(*a), a->pair_grads && a->grad_sums && a->d_features, me)) return st;
   if (a->channel_count < 1 || a->channel_count > GS_FEATURE_CHUNK || a->channel_begin < 0 ||
       a->channel_begin + a->channel_count > GS_MAX_FEATURE_CHANNELS ||
       a->d_features_stride < a->channel_begin + a->channel_count)
     return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: channels [channel_begin, channel_begin + channel_count) must be "
                 "1..4 columns inside a d_features row", me);
   if (a->n == 0) return GS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  // (k_gather_slots' lanes per Gaussian for the same partial_groups)
-  if (a->partial_groups == 1)
-    k_gather_feat<1, 4><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else if (a->partial_groups == 2)
-    k_gather_feat<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else
-    k_gather_feat<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  gather_dispatch(slot_lists(*a), [&](auto ql, auto hl, unsigned blocks) {
+    k_gather_feat<decltype(ql)::value, decltype(hl)::value><<<blocks, kBlock, 0, (hipStream_t)stream>>>(*a);
+  });
   return gs_internal_check_launch(me);
 }
 
@@ -909,19 +856,13 @@ gs_status gs_contrib_accumulate(const gs_contrib_gather_args *a, gs_stream_t str
   const char *me = "gs_contrib_accumulate";
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", me);
   if (a->n < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: negative n", me);
-  if (!a->vis || !a->rects || !a->pair_offset || !a->partials || !a->slot_live || !a->weight_sum || !a->weight_max ||
-      !a->pixels || !a->views)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer", me);
-  if (a->partial_groups < 1) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: partial_groups < 1", me);
+  if (const gs_status st = slot_lists_check(
+          slot_lists(*a), a->partials && a->weight_sum && a->weight_max && a->pixels && a->views, me))
+    return st;
   if (a->n == 0) return GS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  // (k_gather_slots' lanes per Gaussian for the same partial_groups)
-  if (a->partial_groups == 1)
-    k_contrib_gather<1, 4><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else if (a->partial_groups == 2)
-    k_contrib_gather<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else
-    k_contrib_gather<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  gather_dispatch(slot_lists(*a), [&](auto ql, auto hl, unsigned blocks) {
+    k_contrib_gather<decltype(ql)::value, decltype(hl)::value><<<blocks, kBlock, 0, (hipStream_t)stream>>>(*a);
+  });
   return gs_internal_check_launch(me);
 }
 

@@ -14,6 +14,7 @@
 #include "gsplat_mi355x.h"
 #include "gs_internal.h"
 #include "gs_device.h"
+#include "gs_gather_device.h"
 
 namespace {
 
@@ -22,15 +23,6 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) {
 }
 
 // ------------------------------------------------------------ geometry ----
-__device__ __forceinline__ void unpack_rect(const uint32_t *rects, uint32_t g, int &tx0, int &tx1,
-                                            int &ty0, int &ty1) {
-  const uint2 r = reinterpret_cast<const uint2 *>(rects)[g];
-  tx0 = (int)(r.x & 0xFFFFu);
-  tx1 = (int)(r.x >> 16);
-  ty0 = (int)(r.y & 0xFFFFu);
-  ty1 = (int)(r.y >> 16);
-}
-
 // Sigma = R(normalize(q)) diag(exp(s)^2) R^T  (gaussian_model.py:200-207,
 // math_utils.py:10-26), fp32 in the reference's order.
 __device__ __forceinline__ void cov_from_raw(const float *sc, const float *rq, float S[9]) {
@@ -304,106 +296,21 @@ __global__ __launch_bounds__(kBlock) void k_project_fwd(gs_project_args a) {
 }
 
 // ======================================================== project bwd =====
-// Sum of each Gaussian's gradient partials: QL x HL lanes per Gaussian, lane
-// (h, q) walks g's slots h, h+HL, h+2HL, ... of [pair_offset[g],
-// pair_offset[g] + touches) and adds the partial groups q, q + QL, ... of
-// each (ng per slot: gs_partial_groups) that slot_live flags (slot order),
-// then the lane sums are added in a fixed DPP order -- bitwise reproducible.
-// The q lanes of a slot read its partial record together, and consecutive
-// Gaussians' slots are adjacent (index-order slots): coalesced.  Flags of up
-// to kGatherNB slots are loaded at once, then their partials: two round trips
-// per kGatherNB x HL slots of g (the mean is 4.4 on C3).  Partials are 40 B, 8-B aligned:
-// read as float2.
-
-constexpr int kGatherHL1 = 4;  // slot lanes per Gaussian with one partial group per slot
-
+// Sum of each Gaussian's gradient partials (ng per slot: gs_partial_groups):
+// slot_walk of gs_gather_device.h over the dense 40-B partials.  Flags of up
+// to kGatherNB slots are loaded at once, then their live partials: two round
+// trips per kGatherNB x HL slots of g (the mean is 4.4 on C3).
 constexpr int kF2 = GS_PAIR_GRAD_FLOATS / 2;
+__host__ __device__ __forceinline__ SlotLists slot_lists(const gs_project_bwd_args &a, int ng) {
+  return {a.g.n, a.vis, a.rects, a.pair_offset, a.slot_live, ng};
+}
 
-// Gaussian g's partials summed by its QL x HL lanes (lane (h, q) of g at
-// t % LPG); every one of the LPG lanes returns the sum in acc.
-// Slots per lane per round trip: 3 (56 VGPRs, 8 waves per SIMD) against 4
-// (71, 7 waves): 110.9 -> 105.9 us at C3 (profiles/r05/gather_nb_ab/); the
-// lane's slot order, and so every sum, is the same for any batch size.
-#ifndef GS_GATHER_NB
-#define GS_GATHER_NB 3
-#endif
-constexpr int kGatherNB = GS_GATHER_NB;
 // Gather mode (compile time: a runtime test costs the latency-bound gather
 // ~5 us at C3, measured for a status word's scalar load on every wave's path):
 // kGatherOrder -- the Gaussians walked in gs_project_bwd_args.order.  (A
 // failed device-resident frame needs no test here: its emission cleared the
 // rectangles, so every Gaussian gathers zero slots, gs_bin_args.device_counts.)
 constexpr int kGatherOrder = 2;
-template <int QL, int HL, int kNG, int kMode>
-__device__ __forceinline__ void gather_slots(const gs_project_bwd_args &a, uint32_t ng, long long t, int g,
-                                             float2 acc[kF2]) {
-  constexpr int LPG = QL * HL;
-  static_assert(LPG == 2 || LPG == 4 || LPG == 8, "lanes per Gaussian");
-  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
-#pragma unroll
-  for (int k = 0; k < kF2; ++k) acc[k] = make_float2(0.f, 0.f);
-  // vis, rect and first slot in one round trip (the empty asm keeps the
-  // slot load beside the others: used only under the branch, the compiler
-  // would issue it after the vis test, a second round trip)
-  const bool valid = g < a.g.n;
-  const uint32_t gi = valid ? (uint32_t)g : 0u;
-  const uint32_t visb = a.vis[gi];
-  int tx0, tx1, ty0, ty1;
-  unpack_rect(a.rects, gi, tx0, tx1, ty0, ty1);
-  uint32_t off32 = a.pair_offset[gi];
-  asm volatile("" : "+v"(off32));
-  const uint32_t cnt = (valid && visb) ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
-  // lane q sums partial groups q, q + QL, ... of a slot's ng (one pass when ng <= QL)
-  for (uint32_t qc = (uint32_t)q; cnt > (uint32_t)h && qc < ng; qc += QL) {
-    const size_t off = off32;
-    const uint8_t *flag = a.slot_live + off * ng + qc;  // (slot e, group qc) at flag[ng e]
-    // group-qc partial of slot e at part + e * ng * GS_PARTIAL_STRIDE (dense 40-B records)
-    const float2 *part = reinterpret_cast<const float2 *>(a.pair_grads + (off * ng + qc) * GS_PARTIAL_STRIDE);
-    for (uint32_t e0 = (uint32_t)h; e0 < cnt; e0 += kGatherNB * HL) {
-      // the batch's flags in one round trip: unconditional loads (past the end
-      // the clamped index re-reads slot e0), masked after
-      uint32_t f[kGatherNB];
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) {
-        const uint32_t e = e0 + HL * i;
-        f[i] = flag[(size_t)ng * (e < cnt ? e : e0)];
-      }
-      // all the batch's flags tested before any partial is requested: the partial
-      // loads are conditional, so a wait for a later flag placed between them
-      // would have to count them out conservatively and drain them
-      uint32_t fm = 0;
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) fm |= (e0 + HL * i < cnt && f[i]) ? 1u << i : 0u;
-      asm volatile("" : "+v"(fm));
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) f[i] = (fm >> i) & 1u;
-      f4_u8 va[kGatherNB], vb[kGatherNB];
-      f2_u8 vc[kGatherNB];
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) {
-        const float *src = reinterpret_cast<const float *>(part + (size_t)(e0 + HL * i) * ng * kF2);
-        // (non-temporal loads, for data read once, measured +10 us: profiles/r03/experiments.md)
-        va[i] = f[i] ? *reinterpret_cast<const f4_u8 *>(src) : f4_u8{0.f, 0.f, 0.f, 0.f};
-        vb[i] = f[i] ? *reinterpret_cast<const f4_u8 *>(src + 4) : f4_u8{0.f, 0.f, 0.f, 0.f};
-        vc[i] = f[i] ? *reinterpret_cast<const f2_u8 *>(src + 8) : f2_u8{0.f, 0.f};
-      }
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) {
-        if (!f[i]) continue;
-        acc[0].x += va[i].x; acc[0].y += va[i].y; acc[1].x += va[i].z; acc[1].y += va[i].w;
-        acc[2].x += vb[i].x; acc[2].y += vb[i].y; acc[3].x += vb[i].z; acc[3].y += vb[i].w;
-        acc[4].x += vc[i].x; acc[4].y += vc[i].y;
-      }
-    }
-  }
-  // the lane sums in a fixed DPP order, on every lane of the Gaussian's LPG
-#pragma unroll
-  for (int k = 0; k < kF2; ++k) {
-    acc[k].x = lanes_sum<LPG>(acc[k].x);
-    acc[k].y = lanes_sum<LPG>(acc[k].y);
-  }
-}
-
 // accumulate: grad_sums = grad_sums + this batch's sums (the cell batches of
 // one backward, added in batch order: deterministic), else grad_sums = them.
 template <int QL, int HL, int kNG = 0, int kMode = 0>  // kNG > 0: the partial groups per slot at compile time (else ng)
@@ -412,77 +319,52 @@ __global__ __launch_bounds__(kBlock) void k_gather_slots(gs_project_bwd_args a, 
   const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
   int g = (int)(t / LPG);
   if ((kMode & kGatherOrder) && g < a.g.n) g = (int)a.order[g];  // (gs_project_bwd_args.order)
-  float2 acc[kF2];
-  gather_slots<QL, HL, kNG, kMode>(a, kNG > 0 ? (uint32_t)kNG : ng_rt, t, g, acc);
-  if ((t % LPG) == 0 && g < a.g.n) {
+  const SlotLists s = slot_lists(a, kNG > 0 ? kNG : (int)ng_rt);
+  const SlotLane l = slot_lane<QL, HL>(s, t, g);
+  float acc[GS_PAIR_GRAD_FLOATS];
+#pragma unroll
+  for (int k = 0; k < GS_PAIR_GRAD_FLOATS; ++k) acc[k] = 0.f;
+  slot_walk<QL, HL, kGatherNB, kLoadLazy>(
+      s, l, [&](size_t i) { return load_partial10(a.pair_grads, i); }, [&](const Partial10 &v) { add_partial10(acc, v); });
+#pragma unroll
+  for (int k = 0; k < GS_PAIR_GRAD_FLOATS; ++k) acc[k] = lanes_sum<LPG>(acc[k]);
+  if ((t % LPG) == 0 && l.valid) {
     float2 *out = reinterpret_cast<float2 *>(a.grad_sums) + (size_t)g * kF2;
     if (accumulate) {
 #pragma unroll
       for (int k = 0; k < kF2; ++k) {
         const float2 o = out[k];
-        out[k] = make_float2(o.x + acc[k].x, o.y + acc[k].y);
+        out[k] = make_float2(o.x + acc[2 * k], o.y + acc[2 * k + 1]);
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < kF2; ++k) out[k] = acc[k];
+      for (int k = 0; k < kF2; ++k) out[k] = make_float2(acc[2 * k], acc[2 * k + 1]);
     }
   }
 }
 
 // The absolute-gradient partials of gs_blend_backward_abs ([T, ng] float2,
-// flagged by the same slot_live) summed per Gaussian: k_gather_slots' lanes
-// and order -- lane (h, q) of g adds the groups q, q + QL, ... of its slots h,
-// h + HL, ... in that order, then the lane sums in the fixed DPP order -- so
-// the sums are bitwise reproducible.  8 B per partial, a fifth of
-// k_gather_slots' bytes, but latency decides as there: flags and partials of
-// kGatherNB slots per round trip (one slot at a time took 97.8 us at C3, as
-// long as k_gather_slots).
+// flagged by the same slot_live) summed per Gaussian: the same slot_walk.
+// 8 B per partial, a fifth of k_gather_slots' bytes, but latency decides as
+// there: flags and partials of kGatherNB slots in one round trip (one slot at
+// a time took 97.8 us at C3, as long as k_gather_slots).
 template <int QL, int HL>
 __global__ __launch_bounds__(kBlock) void k_gather_abs(gs_abs_gather_args a) {
   constexpr int LPG = QL * HL;
-  static_assert(LPG == 2 || LPG == 4 || LPG == 8, "lanes per Gaussian");
   const long long t = (long long)blockIdx.x * kBlock + threadIdx.x;
   const int g = (int)(t / LPG);
-  const int h = (int)((t % LPG) / QL), q = (int)(t % QL);
-  const bool valid = g < a.n;
-  const uint32_t gi = valid ? (uint32_t)g : 0u;
-  const uint32_t visb = a.vis[gi];
-  int tx0, tx1, ty0, ty1;
-  unpack_rect(a.rects, gi, tx0, tx1, ty0, ty1);
-  const size_t off = a.pair_offset[gi];
-  const uint32_t cnt = (valid && visb) ? rect_touches(tx0, tx1, ty0, ty1) : 0u;
-  const uint32_t ng = (uint32_t)a.partial_groups;
+  const SlotLists s = slot_lists(a);
+  const SlotLane l = slot_lane<QL, HL>(s, t, g);
   float sx = 0.f, sy = 0.f;
-  for (uint32_t qc = (uint32_t)q; cnt > (uint32_t)h && qc < ng; qc += QL) {
-    const uint8_t *flag = a.slot_live + off * ng + qc;  // (slot e, group qc) at flag[ng e]
-    const float2 *part = reinterpret_cast<const float2 *>(a.abs_grads) + off * ng + qc;
-    for (uint32_t e0 = (uint32_t)h; e0 < cnt; e0 += kGatherNB * HL) {
-      // the batch's flags and partials in one round trip: unconditional loads
-      // (past the end the clamped index re-reads slot e0; a dead partial is
-      // read -- 8 B of whatever the buffer holds -- and never used), masked after
-      uint32_t f[kGatherNB];
-      float2 v[kGatherNB];
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) {
-        const uint32_t e = e0 + HL * i;
-        const size_t at = (size_t)ng * (e < cnt ? e : e0);
-        f[i] = flag[at];
-        v[i] = part[at];
-      }
-      uint32_t fm = 0;
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) fm |= (e0 + HL * i < cnt && f[i]) ? 1u << i : 0u;
-#pragma unroll
-      for (int i = 0; i < kGatherNB; ++i) {
-        if (!((fm >> i) & 1u)) continue;
-        sx += v[i].x;
-        sy += v[i].y;
-      }
-    }
-  }
+  slot_walk<QL, HL, kGatherNB, kLoadEager>(
+      s, l, [&](size_t i) { return reinterpret_cast<const float2 *>(a.abs_grads)[i]; },
+      [&](const float2 &v) {
+        sx += v.x;
+        sy += v.y;
+      });
   sx = lanes_sum<LPG>(sx);
   sy = lanes_sum<LPG>(sy);
-  if ((t % LPG) == 0 && valid) {
+  if ((t % LPG) == 0 && l.valid) {
     float2 *out = reinterpret_cast<float2 *>(a.abs_sums) + g;
     if (a.accumulate) {
       const float2 o = *out;
@@ -1048,21 +930,17 @@ bool filter_ok(const gs_screen_filter &f) { return f.variance >= 0.f && __builti
 // the gather's launch, for gs_gather_partials and the backward entry points
 gs_status launch_gather(const gs_project_bwd_args *a, int accumulate, hipStream_t s) {
   const uint32_t ng = (uint32_t)a->partial_groups;
-  const unsigned gb = div_up(8LL * a->g.n, kBlock);
-  if (a->order) {  // (a walk in another order: the default tile only, a probe's)
-    if (ng != 4)
-      return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: order needs the default tile's 4 partial groups", "gs_gather_partials");
-    k_gather_slots<4, 2, 4, kGatherOrder><<<gb, kBlock, 0, s>>>(*a, ng, accumulate);
-    return gs_internal_check_launch("gs_gather_partials");
-  }
-  if (ng == 1)
-    k_gather_slots<1, kGatherHL1><<<div_up((long long)kGatherHL1 * a->g.n, kBlock), kBlock, 0, s>>>(*a, ng, accumulate);
-  else if (ng == 2)
-    k_gather_slots<2, 2><<<div_up(4LL * a->g.n, kBlock), kBlock, 0, s>>>(*a, ng, accumulate);
-  else if (ng == 4)  // the default tile's four cells
-    k_gather_slots<4, 2, 4><<<div_up(8LL * a->g.n, kBlock), kBlock, 0, s>>>(*a, ng, accumulate);
-  else
-    k_gather_slots<4, 2><<<div_up(8LL * a->g.n, kBlock), kBlock, 0, s>>>(*a, ng, accumulate);
+  // (a walk in another order: the default tile only, a probe's)
+  if (a->order && ng != 4)
+    return gs_internal_fail(GS_ERR_UNSUPPORTED, "%s: order needs the default tile's 4 partial groups", "gs_gather_partials");
+  gather_dispatch(slot_lists(*a, a->partial_groups), [&](auto ql, auto hl, unsigned blocks) {
+    constexpr int QL = decltype(ql)::value, HL = decltype(hl)::value;
+    if constexpr (QL == 4) {  // the default tile's four cells: ng at compile time
+      if (a->order) return k_gather_slots<QL, HL, 4, kGatherOrder><<<blocks, kBlock, 0, s>>>(*a, ng, accumulate);
+      if (ng == 4) return k_gather_slots<QL, HL, 4><<<blocks, kBlock, 0, s>>>(*a, ng, accumulate);
+    }
+    k_gather_slots<QL, HL><<<blocks, kBlock, 0, s>>>(*a, ng, accumulate);
+  });
   return gs_internal_check_launch("gs_gather_partials");
 }
 
@@ -1121,9 +999,8 @@ gs_status gs_project_forward(const gs_project_args *a, gs_stream_t stream) {
 gs_status gs_gather_partials(const gs_project_bwd_args *a, int32_t accumulate, gs_stream_t stream) {
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", "gs_gather_partials");
   if (a->g.n <= 0) return GS_OK;
-  if (!a->pair_grads || !a->slot_live || !a->grad_sums || !a->vis || !a->rects || !a->pair_offset ||
-      a->partial_groups < 1)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer or partial_groups < 1", "gs_gather_partials");
+  if (const gs_status st = slot_lists_check(slot_lists(*a, a->partial_groups), a->pair_grads && a->grad_sums, "gs_gather_partials"))
+    return st;
   return launch_gather(a, accumulate, (hipStream_t)stream);
 }
 
@@ -1132,17 +1009,10 @@ gs_status gs_gather_abs_partials(const gs_abs_gather_args *a, gs_stream_t stream
   if (!a) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null args", what);
   if (a->n < 0) return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: bad n", what);
   if (a->n == 0) return GS_OK;
-  if (!a->abs_grads || !a->slot_live || !a->abs_sums || !a->vis || !a->rects || !a->pair_offset ||
-      a->partial_groups < 1)
-    return gs_internal_fail(GS_ERR_INVALID_ARG, "%s: null buffer or partial_groups < 1", what);
-  hipStream_t s = (hipStream_t)stream;
-  // (k_gather_slots' lanes per Gaussian for the same partial_groups)
-  if (a->partial_groups == 1)
-    k_gather_abs<1, kGatherHL1><<<div_up((long long)kGatherHL1 * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else if (a->partial_groups == 2)
-    k_gather_abs<2, 2><<<div_up(4LL * a->n, kBlock), kBlock, 0, s>>>(*a);
-  else
-    k_gather_abs<4, 2><<<div_up(8LL * a->n, kBlock), kBlock, 0, s>>>(*a);
+  if (const gs_status st = slot_lists_check(slot_lists(*a), a->abs_grads && a->abs_sums, what)) return st;
+  gather_dispatch(slot_lists(*a), [&](auto ql, auto hl, unsigned blocks) {
+    k_gather_abs<decltype(ql)::value, decltype(hl)::value><<<blocks, kBlock, 0, (hipStream_t)stream>>>(*a);
+  });
   return gs_internal_check_launch(what);
 }
 
