@@ -9,6 +9,7 @@ already loaded (libamdhip64.so.7) is the one the library binds to.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import threading
@@ -570,6 +571,29 @@ def load(path: str = LIB_PATH):
                 raise NativeLibraryError(f"{LIB_NAME} ABI {v} != expected {GS_ABI_VERSION}")
             _lib = lib
     return _lib
+
+
+# The two workspaces' layouts by name, in the order of gs_frame_offsets' out[14] and
+# gs_tile_offsets' out[9] (byte offsets; tile `live_words` is a count, the bitmap's row stride).
+FRAME_OFFSET_NAMES = ("records", "rects", "keys", "vals", "key_minmax", "counters", "sort_ws", "bin_ws",
+                      "pair_offset", "ranges", "pix_flags", "cell_neval", "grad_sums", "total")
+TILE_OFFSET_NAMES = ("tk0", "tk1", "tv0", "tv1", "sort_ws", "live", "flags", "total", "live_words")
+FrameOffsets = collections.namedtuple("FrameOffsets", FRAME_OFFSET_NAMES)
+TileOffsets = collections.namedtuple("TileOffsets", TILE_OFFSET_NAMES)
+
+
+def frame_offsets(n: int, width: int, height: int, tile_size: int) -> FrameOffsets:
+    """gs_frame_offsets of a frame of n Gaussians, by name."""
+    out = (C.c_size_t * len(FRAME_OFFSET_NAMES))()
+    load().gs_frame_offsets(n, width, height, tile_size, out)
+    return FrameOffsets(*out)
+
+
+def tile_offsets(capacity: int, num_tiles: int, live_cells: int, flag_groups: int) -> TileOffsets:
+    """gs_tile_offsets of a tile workspace for `capacity` entries, by name."""
+    out = (C.c_size_t * len(TILE_OFFSET_NAMES))()
+    load().gs_tile_offsets(capacity, num_tiles, live_cells, flag_groups, out)
+    return TileOffsets(*out)
 
 
 def check(status: int, what: str):

@@ -158,16 +158,19 @@ def cell_batch(cells: int, entries: int, slot_bytes: int = 41) -> int:
     return max(1, min(cells, PARTIAL_BUDGET_BYTES // per))
 
 
-def flag_bytes(cells: int, cap: int, groups: int = 0) -> int:
-    """Slot-flag bytes that hold [T, frame_groups(T)] for every T <= cap (the
+def flag_groups(cells: int, cap: int, groups: int = 0) -> int:
+    """Slot flags per entry of a tile workspace for `cap` entries (the
+    flag_groups of gs_tile_workspace_bytes): the smallest count whose
+    cap * flag_groups bytes hold [T, frame_groups(T)] for every T <= cap (the
     batch is chosen from the frame's own T, so that the summation order, and
     with it every gradient bit, depends on the frame only -- not on the
     capacity guess of the frame before).  groups: gs_partial_groups."""
     if 0 < groups < cells:
-        return groups * cap  # (combined cells: one batch)
+        return groups  # (combined cells: one batch)
     if cells <= _ALWAYS_ONE_BATCH:
-        return cells * cap
-    return max(min(cells * cap, PARTIAL_BUDGET_BYTES // 41), cap)
+        return cells
+    # T * cell_batch(cells, T) <= max(min(cells * T, budget // 41), T) for every T
+    return max(1, min(cells, -(-(PARTIAL_BUDGET_BYTES // 41) // max(int(cap), 1))))
 
 
 def live_bitmap_bytes(lib, cells: int, entries: int, num_tiles: int) -> int:
@@ -571,7 +574,8 @@ def _distortion_forward(cam: CameraParams, fr: "_Frame", n: int, dp: _Distortion
 
 class _GradSums:
     """One backward's per-Gaussian sums over a stage-path frame, [n,
-    GS_PAIR_GRAD_FLOATS] (allocated on first need), and what every pass needs
+    GS_PAIR_GRAD_FLOATS] (the frame workspace's grad_sums, as
+    gs_render_backward uses it), and what every pass needs
     to add to them: the frame's gather arguments, whether the sums hold
     anything yet (the next gather's `accumulate`), and the colour pass's
     partial buffer -- with its flags while its one batch is not yet gathered."""
@@ -584,7 +588,7 @@ class _GradSums:
     @property
     def sums(self) -> torch.Tensor:
         if self._sums is None:
-            self._sums = torch.empty((self.n, N.GS_PAIR_GRAD_FLOATS), dtype=torch.float32, device=self.dev)
+            self._sums = self.fr.grad_sums
         return self._sums
 
     def accumulate(self) -> int:
@@ -649,10 +653,80 @@ def _distortion_backward(lib, cam: CameraParams, fr: "_Frame", dist: _Distortion
     StageTimer.mark("~end_distortion_bwd")
 
 
+_FRAME_LAYOUTS: dict = {}  # (n, W, H, tile) -> N.FrameOffsets (.total: gs_frame_workspace_bytes)
+
+
+def _frame_layout(n: int, W: int, H: int, tile: int) -> "N.FrameOffsets":
+    key = (n, W, H, tile)
+    fo = _FRAME_LAYOUTS.get(key)
+    if fo is None:
+        fo = _FRAME_LAYOUTS[key] = N.frame_offsets(n, W, H, tile)
+    return fo
+
+
 class _Frame:
-    """Intermediate device buffers of one forward, kept for the backward."""
-    __slots__ = ("records", "rects", "vis", "pair_offset", "order", "ranges", "sorted_gauss", "pix_flags",
-                 "cell_neval", "live_bits", "big", "M", "T", "slot_live", "groups", "consumed", "distortion")
+    """One forward's state for its backward and the replays, whichever host
+    path made it (calls: gs_render_forward did): the camera, the frame
+    workspace (per Gaussian and per pixel) and the tile workspace (per list
+    entry) as the library lays them out (fb: their gs_frame_buffers), and what
+    the forward learned -- M, T, which ping-pong halves hold the sorted ids
+    (depth_alt, tile_alt), and groups, the backward's partials per entry and
+    batch.  flags_zeroed: the slot flags still hold the forward's zeros (a
+    forward with need_grad, until the first backward's colour pass).  The
+    buffers are views made on demand from the named offsets (fo, to)."""
+    __slots__ = ("cam", "fb", "fo", "frame_ws", "tile_ws", "n", "M", "T", "groups", "depth_alt", "tile_alt", "vis",
+                 "flags_zeroed", "distortion", "calls", "tiles", "cells", "_to")
+
+    def __init__(self, cam: CameraParams, n: int, vis, calls: bool):
+        """A frame of n Gaussians with its frame workspace; the forward fills in the rest."""
+        self.cam, self.n, self.vis, self.calls = cam.to_struct(), n, vis, calls
+        self.tiles, self.cells, self.groups = cam.tiles_x * cam.tiles_y, cam.cells, cam.groups
+        self.fo = _frame_layout(n, int(cam.image_width), int(cam.image_height), cam.tile_size)
+        self.frame_ws = torch.empty((self.fo.total,), dtype=torch.uint8, device=vis.device)
+        self.fb = self.tile_ws = self.distortion = self._to = None
+        self.M = self.T = self.depth_alt = self.tile_alt = 0
+        self.flags_zeroed = False
+
+    @property
+    def to(self) -> "N.TileOffsets":
+        """The layout of tile_ws, the workspace fb names."""
+        if self._to is None:
+            fb = self.fb
+            self._to = N.tile_offsets(fb.capacity, self.tiles, fb.live_cells, fb.flag_groups)
+        return self._to
+
+    def _f(self, off, nbytes, dtype, shape):
+        return self.frame_ws[off:off + nbytes].view(dtype).view(shape)
+
+    def _t(self, off, nbytes, dtype, shape):
+        return self.tile_ws[off:off + nbytes].view(dtype).view(shape)
+
+    records = property(lambda s: s._f(s.fo.records, 4 * N.GS_RECORD_FLOATS * s.n, torch.float32,
+                                      (s.n, N.GS_RECORD_FLOATS)))
+    rects = property(lambda s: s._f(s.fo.rects, 8 * s.n, torch.int32, (s.n, 2)))
+    order = property(lambda s: s._f(s.fo.vals, 8 * s.n, torch.int32, (2, s.n))[s.depth_alt])
+    counters = property(lambda s: s._f(s.fo.counters, 4 * N.GS_NUM_COUNTERS, torch.int32, (N.GS_NUM_COUNTERS,)))
+    pair_offset = property(lambda s: s._f(s.fo.pair_offset, 4 * s.n, torch.int32, (s.n,)))
+    ranges = property(lambda s: s._f(s.fo.ranges, 8 * s.tiles, torch.int32, (s.tiles, 2)))
+    pix_flags = property(lambda s: s._f(s.fo.pix_flags, s.cam.image_width * s.cam.image_height, torch.uint8, (-1,)))
+    cell_neval = property(lambda s: s._f(s.fo.cell_neval, 4 * s.tiles * s.cells, torch.int32, (s.tiles, s.cells)))
+    grad_sums = property(lambda s: s._f(s.fo.grad_sums, 4 * N.GS_PAIR_GRAD_FLOATS * s.n, torch.float32,
+                                        (s.n, N.GS_PAIR_GRAD_FLOATS)))
+    sorted_gauss = property(lambda s: s._t(s.to.tv1 if s.tile_alt else s.to.tv0, 4 * s.T, torch.int32, (s.T,)))
+    live_bits = property(lambda s: s._t(s.to.live, 8 * s.cells * s.to.live_words, torch.int64,
+                                        (s.cells, s.to.live_words)) if s.fb.live_cells else None)
+    slot_live = property(lambda s: s._t(s.to.flags, s.groups * s.T, torch.uint8, (s.groups * s.T,)))
+
+
+class _FastFrame(_Frame):
+    """A _Frame with `calls` set, under the name the call path's frame had
+    before, plus fa, the arguments gs_render_forward filled in (the depth-bit
+    range it reported: tests/device_frame_util.host_frame compares it with the
+    device-resident frame's).  Tests written against the two former classes
+    tell a call-path frame by isinstance(fr, _FastFrame) and read fr.fa; they
+    keep passing.  The state and the views are _Frame's, and nothing in the
+    package tells the two apart."""
+    __slots__ = ("fa",)
 
 
 _T_SEEN: dict = {}  # device -> tile entries T of its last frame (capacity guess)
@@ -847,45 +921,6 @@ def _frame_done(dev, T: int, zmin_bits: int, zmax_bits: int) -> None:
     _record_depths(dev, zmin_bits, zmax_bits)
 
 
-def _alloc_tile_buffers(lib, cap: int, num_tiles: int, cam: CameraParams, dev):
-    """One byte buffer for T <= cap entries: tile keys + Gaussian ids
-    (ping-pong, 16 B/entry), the tile sort's workspace, the liveness bitmap
-    (cells x gs_blend_live_words, within LIVE_BUDGET_BYTES) and the backward's
-    slot flags (the first cell batch's groups, B/entry)."""
-    nbytes = (16 * cap + 255) // 256 * 256
-    nbytes += (int(lib.gs_radix_sort_workspace_bytes(cap)) + 255) // 256 * 256
-    nbytes += live_bitmap_bytes(lib, cam.cells, cap, num_tiles)
-    nbytes += (flag_bytes(cam.cells, cap, cam.groups) + 255) // 256 * 256  # slot flags (zeroed by gs_tile_ranges)
-    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), cap
-
-
-class _TileLayout:
-    """Addresses inside one _alloc_tile_buffers allocation of capacity `cap`:
-    tile keys and Gaussian ids (ping-pong), the tile sort's workspace, the
-    liveness bitmap (stride live_words, sized for `cap` entries)."""
-    __slots__ = ("big", "cap", "p_tk", "p_tv", "p_ws", "ws_bytes", "o_live", "p_live", "live_words", "bits",
-                 "o_flags", "groups")
-
-
-def _tile_layout(lib, buf, num_tiles: int, cam: CameraParams) -> _TileLayout:
-    big, cap = buf
-    L = _TileLayout()
-    L.big, L.cap = big, cap
-    base = big.data_ptr()
-    L.p_tk = (base, base + 4 * cap)             # tile keys, ping-pong
-    L.p_tv = (base + 8 * cap, base + 12 * cap)  # Gaussian ids, ping-pong
-    o_ws = (16 * cap + 255) // 256 * 256
-    L.ws_bytes = int(lib.gs_radix_sort_workspace_bytes(cap))  # (>= what any T <= cap needs)
-    L.o_live = o_ws + (L.ws_bytes + 255) // 256 * 256
-    live_bytes = live_bitmap_bytes(lib, cam.cells, cap, num_tiles)
-    L.p_ws, L.p_live = base + o_ws, (base + L.o_live if live_bytes else None)
-    L.live_words = int(lib.gs_blend_live_words(cap, num_tiles)) if live_bytes else 0
-    L.o_flags = L.o_live + live_bytes
-    L.groups = 0  # the backward's partials per entry and batch: frame_groups(T), set once T is known
-    L.bits = max(1, int(math.ceil(math.log2(num_tiles))) if num_tiles > 1 else 1)
-    return L
-
-
 # Frames at the default tile run through the library's frame entry points
 # (gs_render_forward / gs_render_backward: one call per direction over two
 # workspaces, ABI 18) unless GS_FRAME_CALLS=0; other tile sizes, and hosts
@@ -896,47 +931,6 @@ _FRAME_CALLS = os.environ.get("GS_FRAME_CALLS", "1") != "0"
 # gs_render_forward's patience with the counter poll before it synchronises the
 # stream and looks once more (0: the library's 10 s; tests shorten it)
 _POLL_TIMEOUT_MS = int(os.environ.get("GS_POLL_TIMEOUT_MS", "0"))
-_WS_BYTES: dict = {}  # (n, W, H, tile) -> gs_frame_workspace_bytes
-
-
-class _FastFrame:
-    """One forward's state for its backward, in the frame and tile
-    workspaces (gs_render_forward).  The buffers the tests and the bench
-    inspect are views made on demand (gs_frame_offsets / gs_tile_offsets)."""
-    __slots__ = ("fa", "frame_ws", "tile_ws", "M", "T", "groups", "_off", "_toff", "n", "HW", "tiles", "cells",
-                 "slot_live_zeroed", "vis")
-
-    def _o(self):
-        if self._off is None:
-            lib = N.load()
-            fo = (C.c_size_t * 14)()
-            c = self.fa.cam
-            lib.gs_frame_offsets(self.n, c.image_width, c.image_height, c.tile_size, fo)
-            to = (C.c_size_t * 9)()
-            fb = self.fa.fb
-            lib.gs_tile_offsets(fb.capacity, self.tiles, fb.live_cells, fb.flag_groups, to)
-            self._off, self._toff = list(fo), list(to)
-        return self._off, self._toff
-
-    def _f(self, i, nbytes, dtype, shape):
-        o = self._o()[0][i]
-        return self.frame_ws[o:o + nbytes].view(dtype).view(shape)
-
-    def _t(self, i, nbytes, dtype, shape):
-        o = self._o()[1][i]
-        return self.tile_ws[o:o + nbytes].view(dtype).view(shape)
-
-    records = property(lambda s: s._f(0, 4 * N.GS_RECORD_FLOATS * s.n, torch.float32, (s.n, N.GS_RECORD_FLOATS)))
-    rects = property(lambda s: s._f(1, 8 * s.n, torch.int32, (s.n, 2)))
-    order = property(lambda s: s._f(3, 8 * s.n, torch.int32, (2, s.n))[s.fa.depth_alt])
-    pair_offset = property(lambda s: s._f(8, 4 * s.n, torch.int32, (s.n,)))
-    ranges = property(lambda s: s._f(9, 8 * s.tiles, torch.int32, (s.tiles, 2)))
-    pix_flags = property(lambda s: s._f(10, s.HW, torch.uint8, (s.HW,)))
-    cell_neval = property(lambda s: s._f(11, 4 * s.tiles * s.cells, torch.int32, (s.tiles, s.cells)))
-    sorted_gauss = property(lambda s: s._t(2 + s.fa.tile_alt, 4 * s.T, torch.int32, (s.T,)))
-    live_bits = property(lambda s: s._t(5, 8 * s.cells * s._o()[1][8], torch.int64, (s.cells, s._o()[1][8])))
-    slot_live = property(lambda s: s._t(6, s.groups * s.T, torch.uint8, (s.groups * s.T,)))
-
 
 
 def _host_counters(dev) -> "_HostCounters":
@@ -998,20 +992,16 @@ def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opa
     n = int(xyz.shape[0])
     H, W = int(cam.image_height), int(cam.image_width)
     s = _stream()
-    tiles = cam.tiles_x * cam.tiles_y
-    key = (n, W, H, cam.tile_size)
-    fws = _WS_BYTES.get(key)
-    if fws is None:
-        fws = _WS_BYTES[key] = int(lib.gs_frame_workspace_bytes(n, W, H, cam.tile_size))
     fa = N.GsRenderFwdArgs()
     means2d, conics, radii, vis = gaussian_outs = _gaussian_outputs(n, dev)
     image, alpha, depth = pixel_outs = _pixel_outputs(H, W, dev)
-    frame_ws = torch.empty((fws,), dtype=torch.uint8, device=dev)
+    fr = _FastFrame(cam, n, vis, calls=True)
+    fr.fa = fa
     _bind_frame_args(fa, cam, _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit,
-                                                sh_rest, sh_degree), gaussian_outs, pixel_outs, frame_ws)
+                                                sh_rest, sh_degree), gaussian_outs, pixel_outs, fr.frame_ws)
 
     def tile_workspace(cap):
-        tws = int(lib.gs_tile_workspace_bytes(cap, tiles, cam.cells, cam.groups))
+        tws = int(lib.gs_tile_workspace_bytes(cap, fr.tiles, cam.cells, cam.groups))
         ws = torch.empty((tws,), dtype=torch.uint8, device=dev)
         _bind_tile_ws(fa, ws, cap)
         return ws
@@ -1037,11 +1027,8 @@ def _forward_frame(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, opa
     M, T = int(fa.M), int(fa.T)
     if n > 0:
         _frame_done(dev, T, int(fa.depth_min_bits), int(fa.depth_max_bits))
-    fr = _FastFrame()
-    fr.fa, fr.frame_ws, fr.tile_ws, fr.M, fr.T = fa, frame_ws, tile_ws, M, T
-    fr.groups, fr._off, fr._toff, fr.n, fr.HW, fr.tiles, fr.cells = cam.groups, None, None, n, H * W, tiles, cam.cells
-    fr.slot_live_zeroed = bool(need_grad)
-    fr.vis = vis
+    fr.fb, fr.tile_ws, fr.M, fr.T, fr.depth_alt, fr.tile_alt = fa.fb, tile_ws, M, T, fa.depth_alt, fa.tile_alt
+    fr.flags_zeroed = bool(need_grad)
     if M == 0:
         image, alpha, depth = _empty_frame_outputs(cam, dev)
     return image, alpha, depth, means2d, conics, radii, vis, fr
@@ -1071,82 +1058,76 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
     dev = xyz.device
     n = int(xyz.shape[0])
     H, W = int(cam.image_height), int(cam.image_width)
-    f32, i32 = torch.float32, torch.int32
     s = _stream()
     cs = cam.to_struct()
     gst = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
+    num_tiles = cam.tiles_x * cam.tiles_y
+    bits = max(1, int(math.ceil(math.log2(num_tiles))) if num_tiles > 1 else 1)  # (of the tile sort's keys)
 
+    # the frame workspace holds everything whose size does not depend on T, so
+    # it is allocated before the one host sync: the GPU waits only for the
+    # read-back and launches
     means2d, conics, radii, vis = _gaussian_outputs(n, dev)
-    records = torch.empty((n, N.GS_RECORD_FLOATS), dtype=f32, device=dev)
-    rects = torch.empty((n, 2), dtype=i32, device=dev)
-    keys = torch.empty((2, n), dtype=i32, device=dev)
-    vals = torch.empty((2, n), dtype=i32, device=dev)
-    counters = torch.empty((N.GS_NUM_COUNTERS,), dtype=i32, device=dev)
-    key_minmax = torch.empty((2 * max(1, (n + 255) // 256),), dtype=i32, device=dev)
+    fr = _Frame(cam, n, vis, calls=False)
+    fo, fw = fr.fo, fr.frame_ws.data_ptr()
+    fb = fr.fb = N.GsFrameBuffers(fw, fo.total)
+    keys, vals, key_minmax = fw + fo.keys, fw + fo.vals, fw + fo.key_minmax  # (keys, vals: [2, n] ping-pong)
     window, key_base, key_bits, msd = _depth_keys(dev, depth_window_ok)
 
     StageTimer.mark("project_fwd")
-    pa = N.GsProjectArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(radii), N.ptr(vis), N.ptr(records),
-                         N.ptr(rects), N.ptr(keys[0]), key_base, key_bits, N.ptr(key_minmax), cam.filter_struct())
+    pa = N.GsProjectArgs(cs, gst, N.ptr(means2d), N.ptr(conics), N.ptr(radii), N.ptr(vis), fw + fo.records,
+                         fw + fo.rects, keys, key_base, key_bits, key_minmax, cam.filter_struct())
     N.check(lib.gs_project_forward(C.byref(pa), s), "gs_project_forward")
 
-    fr = _Frame()
-    fr.slot_live = None
-    fr.consumed = False  # (a backward ran: the slot flags hold its last batch's, not the forward's zeros)
-    fr.groups = cam.groups
-    fr.records, fr.rects, fr.vis, fr.order = records, rects, vis, None
+    def tile_workspace(cap: int):
+        """(a tile workspace for `cap` entries, bound to fb; its layout; its tile sort's workspace bytes:
+        what the capacity needs, >= what any T below it does) -- everything the launches after the sync
+        need but T, laid out while the GPU counts and emits"""
+        fb.live_cells = cam.cells if live_bitmap_bytes(lib, cam.cells, cap, num_tiles) else 0
+        fb.flag_groups, fb.capacity = flag_groups(cam.cells, cap, cam.groups), cap
+        to = N.tile_offsets(cap, num_tiles, fb.live_cells, fb.flag_groups)
+        ws = torch.empty((to.total,), dtype=torch.uint8, device=dev)
+        fb.tile_ws, fb.tile_ws_bytes = ws.data_ptr(), to.total
+        ba.tile_keys, ba.pair_gauss, ba.capacity = fb.tile_ws + to.tk0, fb.tile_ws + to.tv0, cap
+        return ws, to, lib.gs_radix_sort_workspace_bytes(cap)
     if n > 0:
-        ws = torch.empty((lib.gs_radix_sort_workspace_bytes(n),), dtype=torch.uint8, device=dev)
         StageTimer.mark("depth_sort")
         alt = C.c_int32(0)
+        ws_bytes = lib.gs_radix_sort_workspace_bytes(n)
         if msd:
-            N.check(lib.gs_depth_sort_msd(N.ptr(keys[0]), N.ptr(vals[0]), N.ptr(keys[1]), N.ptr(vals[1]), n,
-                                          key_bits, N.ptr(ws), ws.numel(), N.ptr(key_minmax) + 4, C.byref(alt),
-                                          s), "depth sort (msd)")
+            N.check(lib.gs_depth_sort_msd(keys, vals, keys + 4 * n, vals + 4 * n, n, key_bits, fw + fo.sort_ws,
+                                          ws_bytes, key_minmax + 4, C.byref(alt), s), "depth sort (msd)")
         else:
-            N.check(lib.gs_radix_sort_pairs(N.ptr(keys[0]), N.ptr(vals[0]), N.ptr(keys[1]), N.ptr(vals[1]), n, 0,
-                                            key_bits, 1, N.ptr(ws), ws.numel(), C.byref(alt), s), "depth sort")
-        sorted_ids = vals[alt.value]
-        fr.order = sorted_ids
-        bws = torch.empty((lib.gs_bin_workspace_bytes(n),), dtype=torch.uint8, device=dev)
-        pair_offset = torch.empty((n,), dtype=i32, device=dev)
-        ba = N.GsBinArgs(n, cam.tiles_x, cam.tiles_y, N.ptr(sorted_ids), N.ptr(rects), N.ptr(vis),
-                         N.ptr(counters), N.ptr(key_minmax), N.ptr(bws), bws.numel(), 0, 0, N.ptr(pair_offset),
-                         N.ptr(records), 0)
+            N.check(lib.gs_radix_sort_pairs(keys, vals, keys + 4 * n, vals + 4 * n, n, 0, key_bits, 1,
+                                            fw + fo.sort_ws, ws_bytes, C.byref(alt), s), "depth sort")
+        fr.depth_alt = alt.value
+        ba = N.GsBinArgs(n, cam.tiles_x, cam.tiles_y, vals + 4 * n * alt.value, fw + fo.rects, N.ptr(vis),
+                         fw + fo.counters, key_minmax, fw + fo.bin_ws, lib.gs_bin_workspace_bytes(n), 0, 0,
+                         fw + fo.pair_offset, fw + fo.records, 0)
         hc = _host_counters(dev)
         hc.arm(ba)
         StageTimer.mark("bin_count")
         N.check(lib.gs_bin_count(C.byref(ba), s), "gs_bin_count")
-        # everything whose size does not depend on T is allocated before the
-        # one host sync, so the GPU waits only for the read-back and launches
-        num_tiles = cam.tiles_x * cam.tiles_y
-        ranges = torch.empty((num_tiles, 2), dtype=i32, device=dev)
         image, alpha, depth = _pixel_outputs(H, W, dev)
-        pix_flags = torch.empty((H * W,), dtype=torch.uint8, device=dev)
-        cell_neval = torch.empty((num_tiles, cam.cells), dtype=i32, device=dev)
-        # the T-sized buffers too, at a capacity guessed from the last frame on
-        # this device, and the emission queued into them before the sync (it
+        # the tile workspace too, at a capacity guessed from the last frame on
+        # this device, and the emission queued into it before the sync (it
         # drops entries past the capacity): its kernel time hides the
         # read-back's round trip.  T above the guess: re-allocate, re-emit.
         cap = _capacity_guess(dev)
-        big_guess = _alloc_tile_buffers(lib, cap, num_tiles, cam, dev) if cap else None
+        if cap:
+            fr.tile_ws, fr._to, sort_bytes = tile_workspace(cap)
         # (M, T) reach the host through pinned memory before the emission is
         # queued, so the host wakes while the GPU still emits: gs_bin_count
         # writes them there itself (_HostCounters) -- or, where the runtime
         # does not map the buffer, a copy in the stream and an event
         ready = None
         if hc.dptr is None:
-            hc.t[:4].copy_(counters[:4], non_blocking=True)
+            hc.t[:4].copy_(fr.counters[:4], non_blocking=True)
             ready = torch.cuda.Event()
             ready.record()
-        if big_guess is not None:
-            gb, gcap = big_guess[0].data_ptr(), big_guess[1]
-            ba.tile_keys, ba.pair_gauss, ba.capacity = gb, gb + 8 * gcap, gcap
+        if cap:
             StageTimer.mark("bin_emit")
             N.check(lib.gs_bin_emit(C.byref(ba), s), "gs_bin_emit")
-            # everything the launches after the sync need but T, laid out now
-            # (the GPU is emitting): after the sync only T is filled in
-            layout = _tile_layout(lib, big_guess, num_tiles, cam)
         StageTimer.mark("~sync")
         M, T, zmin, zmax = hc.wait(dev, ready)  # the one host sync
         if not window_holds(window, zmin, zmax):
@@ -1162,50 +1143,39 @@ def forward_pipeline(cam: CameraParams, xyz, cov3d, scaling, rotation, logits, o
         if n > 0:
             _frame_done(dev, T, zmin, zmax)
         image, alpha, depth = _empty_frame_outputs(cam, dev)
-        fr.pair_offset = torch.zeros((max(n, 1),), dtype=i32, device=dev)
+        fr.pair_offset.zero_()
         return image, alpha, depth, means2d, conics, radii, vis, fr
 
     # Between the host sync and the blend launch the GPU idles: this span
-    # only fills T into the prepared launches (re-emitting first when T
-    # exceeded the guess); views of the buffers are made after the blend is
-    # queued.
-    emitted = big_guess is not None and big_guess[1] >= T
-    if not emitted:
-        layout = _tile_layout(lib, _alloc_tile_buffers(lib, T, num_tiles, cam, dev), num_tiles, cam)
-        ba.tile_keys, ba.pair_gauss, ba.capacity = layout.p_tk[0], layout.p_tv[0], layout.cap
+    # only fills T into the launches (re-emitting first when T exceeded the
+    # guess).
+    if fr.tile_ws is None or fb.capacity < T:
+        fr.tile_ws, fr._to, sort_bytes = tile_workspace(T)
         StageTimer.mark("bin_emit")
         N.check(lib.gs_bin_emit(C.byref(ba), s), "gs_bin_emit")
-    L = layout
-    L.groups = cam.frame_groups(T)  # (from T alone: the gradients' summation order)
-    assert L.groups * T <= flag_bytes(cam.cells, L.cap, cam.groups)
+    to, tw = fr._to, fb.tile_ws
+    G = fr.groups = cam.frame_groups(T)  # (from T alone: the gradients' summation order)
+    assert G * T <= fb.capacity * fb.flag_groups
     alt = C.c_int32(0)
     StageTimer.mark("tile_sort")
-    N.check(lib.gs_radix_sort_pairs(L.p_tk[0], L.p_tv[0], L.p_tk[1], L.p_tv[1], T, 0, L.bits, 0,
-                                    L.p_ws, L.ws_bytes, C.byref(alt), s), "tile sort")
+    N.check(lib.gs_radix_sort_pairs(tw + to.tk0, tw + to.tv0, tw + to.tk1, tw + to.tv1, T, 0, bits, 0, tw + to.sort_ws,
+                                    sort_bytes, C.byref(alt), s), "tile sort")
+    fr.tile_alt = alt.value
     # (with gradients to come: the backward's slot flags zeroed in the same kernel)
-    ra = N.GsRangeArgs(T, num_tiles, L.p_tk[alt.value], N.ptr(ranges),
-                       L.big.data_ptr() + L.o_flags if need_grad else None, L.groups)
+    ra = N.GsRangeArgs(T, num_tiles, tw + (to.tk1 if alt.value else to.tk0), fw + fo.ranges,
+                       tw + to.flags if need_grad else None, G)
+    fr.flags_zeroed = bool(need_grad)
     StageTimer.mark("tile_ranges")
     N.check(lib.gs_tile_ranges(C.byref(ra), s), "gs_tile_ranges")
 
-    fa = N.GsBlendFwdArgs(cs, cam.tiles_x, cam.tiles_y, N.ptr(ranges), L.p_tv[alt.value], N.ptr(records),
-                          N.ptr(image), N.ptr(alpha), N.ptr(depth), N.ptr(pix_flags), N.ptr(cell_neval),
-                          L.p_live, L.live_words, N.ptr(pair_counts), T, N.ptr(pix_neval))
+    fa = N.GsBlendFwdArgs(cs, cam.tiles_x, cam.tiles_y, fw + fo.ranges, tw + (to.tv1 if alt.value else to.tv0),
+                          fw + fo.records, N.ptr(image), N.ptr(alpha), N.ptr(depth), fw + fo.pix_flags,
+                          fw + fo.cell_neval, tw + to.live if fb.live_cells else None, to.live_words,
+                          N.ptr(pair_counts), T, N.ptr(pix_neval))
     StageTimer.mark("blend_fwd")
     N.check(lib.gs_blend_forward(C.byref(fa), s), "gs_blend_forward")
     StageTimer.mark("~end_fwd")
     _frame_done(dev, T, zmin, zmax)  # (the next frame's guesses: after the launches)
-
-    # (the blend is queued: views for the frame cost no GPU idle time now)
-    kv = L.big[:16 * L.cap].view(i32).view(4, L.cap)
-    fr.sorted_gauss = kv[2 + alt.value, :T]
-    fr.live_bits = (L.big[L.o_live:L.o_live + 8 * cam.cells * L.live_words].view(torch.int64)
-                    .view(cam.cells, L.live_words) if L.live_words else None)
-    fr.big = L.big
-    fr.groups = L.groups
-    fr.slot_live = L.big[L.o_flags:L.o_flags + L.groups * T] if need_grad else None
-    fr.pair_offset, fr.ranges = pair_offset, ranges
-    fr.pix_flags, fr.cell_neval = pix_flags, cell_neval
     return image, alpha, depth, means2d, conics, radii, vis, fr
 
 
@@ -1233,7 +1203,7 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
     (optional): called with (lo, hi) once the gradient rows of Gaussians
     [lo, hi) are queued, the last stage running in out["_chunks"] ranges so
     that a range's all-reduce overlaps the next range's kernels."""
-    if isinstance(fr, _FastFrame):
+    if fr.calls:
         return _backward_frame(cam, fr, xyz, cov3d, scaling, rotation, logits, opacity, means2d, conics, g_image,
                                g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
                                outputs, d_view, density)
@@ -1259,14 +1229,13 @@ def backward_pipeline(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotati
         # PARTIAL_BUDGET_BYTES), each summed by gs_gather_partials in order.
         G, Q = fr.groups, cam.cells
         pair_grads = torch.empty((fr.T * G, N.GS_PARTIAL_STRIDE), dtype=f32, device=dev)
-        slot_live = fr.slot_live  # (zeroed by the forward's gs_tile_ranges)
-        if slot_live is None:
-            slot_live = torch.zeros((fr.T * G,), dtype=torch.uint8, device=dev)
-        elif fr.consumed:
-            # a second backward of the frame (retain_graph): the flags hold the
-            # last batch's, in that batch's layout
+        slot_live = fr.slot_live
+        if not fr.flags_zeroed:
+            # no gs_tile_ranges zeroed them, or a backward of the frame ran
+            # before (retain_graph): the flags hold its last batch's, in that
+            # batch's layout
             slot_live.zero_()
-        fr.consumed = True
+        fr.flags_zeroed = False
         ba = N.GsBlendBwdArgs(cs, cam.tiles_x, cam.tiles_y, N.ptr(fr.ranges), N.ptr(fr.sorted_gauss),
                               N.ptr(fr.records), N.ptr(image), N.ptr(alpha), N.ptr(depth),
                               N.ptr(fr.pix_flags), N.ptr(fr.cell_neval), N.ptr(g_image), N.ptr(g_alpha), N.ptr(g_depth), N.ptr(fr.live_bits),
@@ -1403,7 +1372,7 @@ def _blend_outputs(outputs):
     return image, alpha, depth
 
 
-def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rotation, logits, opacity, means2d,
+def _backward_frame(cam: CameraParams, fr: _Frame, xyz, cov3d, scaling, rotation, logits, opacity, means2d,
                     conics, g_image, g_alpha, g_depth, g_means2d, g_conics, opacity_is_logit, sh_rest, sh_degree, out,
                     outputs, d_view=None, density=None):
     """backward_pipeline through gs_render_backward (the frame of
@@ -1417,11 +1386,12 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
     s = _stream()
     pixel_grads = g_image is not None or g_alpha is not None or g_depth is not None
     ba = N.GsRenderBwdArgs()
-    fa = fr.fa
-    ba.cam, ba.fb, ba.M, ba.T, ba.tile_alt = fa.cam, fa.fb, fr.M, fr.T, fa.tile_alt
+    ba.cam, ba.fb, ba.M, ba.T, ba.tile_alt = fr.cam, fr.fb, fr.M, fr.T, fr.tile_alt
     # (the forward's Gaussians: the tensors autograd saved for this backward)
-    ba.g, ba.means2d, ba.conics, ba.vis = fa.g, fa.means2d, fa.conics, fa.vis
-    ba.filter = fa.filter
+    ba.g = _gaussians_struct(n, xyz, cov3d, scaling, rotation, logits, opacity, opacity_is_logit, sh_rest, sh_degree)
+    ba.means2d, ba.conics, ba.vis = N.ptr(means2d), N.ptr(conics), N.ptr(fr.vis)
+    if cam.screen_filter:  # (ba is zeroed: no filter)
+        ba.filter = cam.filter_struct()
     pair_grads = None
     if fr.M > 0 and fr.T > 0 and pixel_grads:
         g_image, g_alpha, g_depth, image, alpha, depth = _pixel_cotangents(cam, g_image, g_alpha, g_depth, outputs,
@@ -1430,8 +1400,8 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
         ba.image, ba.alpha, ba.depth = image.data_ptr(), alpha.data_ptr(), depth.data_ptr()
         ba.g_image, ba.g_alpha, ba.g_depth = N.ptr(g_image), N.ptr(g_alpha), N.ptr(g_depth)
         ba.pair_grads = pair_grads.data_ptr()
-        ba.flags_zeroed = 1 if fr.slot_live_zeroed else 0
-        fr.slot_live_zeroed = False  # (a second backward of the frame clears its flags first: ADVICE r05)
+        ba.flags_zeroed = 1 if fr.flags_zeroed else 0
+        fr.flags_zeroed = False  # (a second backward of the frame clears its flags first: ADVICE r05)
     gm = None if g_means2d is None else g_means2d.contiguous()
     gc = None if g_conics is None else g_conics.contiguous()
     ba.g_means2d, ba.g_conics = N.ptr(gm), N.ptr(gc)
@@ -1454,12 +1424,11 @@ def _backward_frame(cam: CameraParams, fr: _FastFrame, xyz, cov3d, scaling, rota
         return grads
     # the projection backward from here: per row range, each range's
     # reduction issued as soon as its rows are queued, or with the pose gradient
-    fo = fr._o()[0]
-    fws = fr.frame_ws.data_ptr()
-    pb = N.GsProjectBwdArgs(fa.cam, ba.g, N.ptr(means2d), N.ptr(conics), fa.vis, fws + fo[1], fws + fo[8], None,
+    fo, fws = fr.fo, fr.frame_ws.data_ptr()
+    pb = N.GsProjectBwdArgs(fr.cam, ba.g, ba.means2d, ba.conics, ba.vis, fws + fo.rects, fws + fo.pair_offset, None,
                             None, N.ptr(gm),
                             N.ptr(gc), N.ptr(d_xyz), N.ptr(d_cov), N.ptr(d_scl), N.ptr(d_rot), N.ptr(d_col),
-                            N.ptr(d_op), N.ptr(d_sh), None, sums, 0, fa.filter)
+                            N.ptr(d_op), N.ptr(d_sh), None, sums, 0, ba.filter)
     _project_backward_ranges(lib, pb, n, chunks, rows_ready, d_view, s)
     if density is not None:
         _accumulate_density(lib, cam, density[0], n, fr.vis, density[1], sums, gm, s)

@@ -143,7 +143,7 @@ def host_frame(pkg, model, cam, cot=None):
     with torch.no_grad():
         img, al, dp, m2, cn, rd, vi, fr = RZ.forward_pipeline(cam, *raw, opacity_is_logit=True, depth_window_ok=False,
                                                               need_grad=cot is not None)
-    assert isinstance(fr, RZ._FastFrame), "the host path of these tests is the frame entry points'"
+    assert fr.calls is True, "the host path of these tests is the frame entry points'"
     h = SimpleNamespace(image=img, alpha=al, depth=dp, means2d=m2, conics=cn, radii=rd, vis=vi, fr=fr, M=int(fr.M),
                         T=int(fr.T), zmin=int(fr.fa.depth_min_bits), zmax=int(fr.fa.depth_max_bits), grads=None)
     if h.M > 0:
@@ -181,7 +181,7 @@ def _bind(pkg, cuda, model, cam, capacity, window, msd, hc):
     n, H, W = int(model._xyz.shape[0]), cam.image_height, cam.image_width
     tiles, cells, groups = cam.tiles_x * cam.tiles_y, cam.cells, cam.groups
     f = SimpleNamespace(n=n, H=H, W=W, tiles=tiles, cells=cells, groups=groups, capacity=int(capacity), lib=lib,
-                        window=window, hc=hc, model=model, cam=cam)
+                        native=N, window=window, hc=hc, model=model, cam=cam)
     f.frame_ws = _Guarded(lib.gs_frame_workspace_bytes(n, W, H, cam.tile_size), FILL, cuda)
     f.tile_ws = _Guarded(lib.gs_tile_workspace_bytes(capacity, tiles, cells, groups), FILL, cuda)
     f.pair_grads = _Guarded(capacity * groups * N.GS_PARTIAL_STRIDE * 4, 0xFF, cuda)
@@ -255,25 +255,26 @@ def device_frame(pkg, cuda, model, cam, capacity, window=None, msd=False, words=
 
 
 def _read_back(f):
-    lib, n, cap = f.lib, f.n, f.capacity
-    fo, to = (C.c_size_t * 14)(), (C.c_size_t * 9)()
-    lib.gs_frame_offsets(n, f.W, f.H, f.cam.tile_size, fo)
-    lib.gs_tile_offsets(cap, f.tiles, f.cells, f.groups, to)
-    assert fo[13] == f.frame_ws.nbytes and to[7] == f.tile_ws.nbytes
+    n, cap = f.n, f.capacity
+    N = f.native
+    fo = N.frame_offsets(n, f.W, f.H, f.cam.tile_size)
+    to = N.tile_offsets(cap, f.tiles, f.cells, f.groups)
+    assert fo.total == f.frame_ws.nbytes and to.total == f.tile_ws.nbytes
     fw, tw = f.frame_ws.view, f.tile_ws.view
 
     def words(buf, off, count):
         return buf[off:off + 4 * count].view(torch.int32).cpu().numpy().view(np.uint32)
-    f.counters = [int(v) for v in words(fw, fo[5], 6)]
+    f.counters = [int(v) for v in words(fw, fo.counters, 6)]
     f.M, f.T, f.zmin, f.zmax, f.status, f.T_eff = f.counters
-    f.rects = fw[fo[1]:fo[1] + 8 * n].view(torch.int32).view(n, 2).clone()
-    f.records = fw[fo[0]:fo[0] + 48 * n].view(torch.float32).view(n, 12).clone()
-    f.pair_offset = fw[fo[8]:fo[8] + 4 * n].view(torch.int32).clone()
-    f.ranges = fw[fo[9]:fo[9] + 8 * f.tiles].view(torch.int32).view(f.tiles, 2).clone()
+    f.rects = fw[fo.rects:fo.rects + 8 * n].view(torch.int32).view(n, 2).clone()
+    f.records = fw[fo.records:fo.records + 48 * n].view(torch.float32).view(n, 12).clone()
+    f.pair_offset = fw[fo.pair_offset:fo.pair_offset + 4 * n].view(torch.int32).clone()
+    f.ranges = fw[fo.ranges:fo.ranges + 8 * f.tiles].view(torch.int32).view(f.tiles, 2).clone()
     alt = int(f.fa.tile_alt)
-    f.tile_halves = [words(tw, to[i], cap) for i in range(4)]  # keys 0 / 1, Gaussian ids 0 / 1, all `cap` entries
+    # keys 0 / 1, Gaussian ids 0 / 1, all `cap` entries
+    f.tile_halves = [words(tw, off, cap) for off in (to.tk0, to.tk1, to.tv0, to.tv1)]
     f.sorted_keys, f.sorted_gauss = f.tile_halves[alt], f.tile_halves[2 + alt]
-    f.slot_flags = tw[to[6]:to[6] + cap * f.groups].cpu().numpy()
+    f.slot_flags = tw[to.flags:to.flags + cap * f.groups].cpu().numpy()
     f.pinned = None
     if f.hc.dptr is not None:
         f.pinned = [int(v) & 0xFFFFFFFF for v in f.hc.np[:8].tolist()]

@@ -104,6 +104,59 @@ def test_cell_batches_and_bitmap_budget(pkg):
     assert 0 < small <= RZ.LIVE_BUDGET_BYTES
 
 
+@pytest.mark.parametrize("n,W,H,tile", [(0, 64, 48, 16), (300, 64, 48, 20), (1_000_000, 1920, 1080, 16)])
+def test_named_workspace_offsets(pkg, n, W, H, tile):
+    """_native.frame_offsets / tile_offsets name gs_frame_offsets' and
+    gs_tile_offsets' arrays in the library's order: the byte offsets do not
+    decrease along the tuple, are 256-aligned, and `total` is what the sizing
+    call returns -- with and without a liveness bitmap."""
+    N, RZ = pkg._native, pkg.rasterizer
+    lib = N.load()
+    assert N.FRAME_OFFSET_NAMES == ("records", "rects", "keys", "vals", "key_minmax", "counters", "sort_ws", "bin_ws",
+                                    "pair_offset", "ranges", "pix_flags", "cell_neval", "grad_sums", "total")
+    assert N.TILE_OFFSET_NAMES == ("tk0", "tk1", "tv0", "tv1", "sort_ws", "live", "flags", "total", "live_words")
+    fo = N.frame_offsets(n, W, H, tile)
+    assert fo._fields == N.FRAME_OFFSET_NAMES
+    assert list(fo) == sorted(fo) and all(o % 256 == 0 for o in fo)
+    assert fo.total == lib.gs_frame_workspace_bytes(n, W, H, tile)
+    tiles, cells = -(-W // tile) * -(-H // tile), (-(-tile // 8)) ** 2
+    for cap in (1, 4096, 4_411_397):
+        groups = RZ.flag_groups(cells, cap, lib.gs_partial_groups(tile))
+        for live_cells in (0, cells):
+            to = N.tile_offsets(cap, tiles, live_cells, groups)
+            assert to._fields == N.TILE_OFFSET_NAMES
+            offsets = list(to[:-1])  # (live_words is a count)
+            assert offsets == sorted(offsets) and all(o % 256 == 0 for o in offsets)
+            assert to.total == lib.gs_tile_workspace_bytes(cap, tiles, live_cells, groups)
+            assert to.live_words == (lib.gs_blend_live_words(cap, tiles) if live_cells else 0)
+            assert to.flags - to.live >= 8 * live_cells * to.live_words and to.total - to.flags >= cap * groups
+
+
+@pytest.mark.parametrize("cap", (1, 4096, 4_411_397))
+@pytest.mark.parametrize("cells", (1, 4, 9, 1444, 57_600))
+def test_flag_groups_hold_every_frame(pkg, cells, cap):
+    """rasterizer.flag_groups: cap * flag_groups slot flags hold [T,
+    frame_groups(T)] at T = cap and at T = 1, in no more flags per entry than
+    the byte count the stage path allocated before the tile workspace carried
+    them (that rule, restated here)."""
+    RZ = pkg.rasterizer
+    tile = 8 * math.isqrt(cells)
+    cam = RZ.CameraParams(1920, 1080, 1000.0, 1000.0, 960.0, 540.0, (1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0),
+                          (0.0, 0.0, 0.0), tile_size=tile)
+    assert cam.cells == cells
+    groups, budget = cam.groups, RZ.PARTIAL_BUDGET_BYTES
+    fg = RZ.flag_groups(cells, cap, groups)
+    for T in (cap, 1):
+        assert cap * fg >= cam.frame_groups(T) * T
+    if 0 < groups < cells:
+        flag_bytes = groups * cap
+    elif cells <= 4:
+        flag_bytes = cells * cap
+    else:
+        flag_bytes = max(min(cells * cap, budget // 41), cap)
+    assert 1 <= fg <= -(-flag_bytes // cap)
+
+
 def test_gaussian_model_layout(pkg):
     """test_gaussian_model.py:35-72 restated for this package's model."""
     m = pkg.GaussianModel()

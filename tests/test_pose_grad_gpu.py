@@ -300,7 +300,7 @@ def test_row_callback_runs_once_over_every_row(pkg, cuda, frame_calls):
         RZ._FRAME_CALLS = frame_calls
         for pose in (True, False):
             img, al, dp, m2, cn, rd, vi, fr = RZ.forward_pipeline(cam, *raw, opacity_is_logit=True, need_grad=True)
-            assert isinstance(fr, RZ._FastFrame) == frame_calls
+            assert fr.calls == frame_calls
             seen = []
             d_view = torch.full((12,), float("nan"), device=cuda) if pose else None
             d = RZ.backward_pipeline(cam, fr, *raw, m2, cn, torch.ones_like(img), None, None, None, None,

@@ -1,14 +1,18 @@
-"""Bitwise comparison of two library builds on the C3 frame (GPU tool).
+"""Bitwise comparison of two library builds (or two host paths) on one frame,
+the C3 frame by default (GPU tool).
 
     GS_LIB_PATH=ab/base.so python tools/bitcmp.py dump gpurun_out/a.npz
     python tools/bitcmp.py dump gpurun_out/b.npz          # in-tree library
     python tools/bitcmp.py cmp gpurun_out/a.npz gpurun_out/b.npz
+    GS_FRAME_CALLS=0 python tools/bitcmp.py dump small.npz --n 300 --size 64x48 --tile 20
 
 A refactor claimed bit-identical (same fp32 operations, reordered or
 re-encoded) must show zero differing elements here: forward outputs and
-every gradient of a fixed random cotangent."""
+every gradient of a fixed random cotangent.  --tile renders through
+rasterize() at that tile edge (any size; small frames with --n / --size)."""
 from __future__ import annotations
 
+import argparse
 import os
 import sys
 
@@ -18,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def dump(path, n=1_000_000, W=1920, H=1080):
+def dump(path, n=1_000_000, W=1920, H=1080, tile=None):
     import torch
     import __graft_entry__ as ge
     pkg = ge.load_package()
@@ -31,7 +35,14 @@ def dump(path, n=1_000_000, W=1920, H=1080):
 
         def world_view_transform(self):
             return torch.eye(4)
-    out = pkg.GaussianRenderer().render(Cam(), m, pkg.RenderSettings(H, W, torch.tensor([0.1, 0.2, 0.3])))
+    st = pkg.RenderSettings(H, W, torch.tensor([0.1, 0.2, 0.3]))
+    if tile is None:
+        out = pkg.GaussianRenderer().render(Cam(), m, st)
+    else:
+        names = ("image", "alpha", "depth", "viewspace_points", "conics")
+        out = dict(zip(names, pkg.rasterizer.rasterize(pkg.camera_params(Cam(), st, tile_size=tile), m._xyz, None,
+                                                       m._scaling, m._rotation, m._features_dc[:, 0, :], m._opacity,
+                                                       opacity_is_logit=True)))
     g = torch.Generator().manual_seed(1)
     cot = [(torch.rand(s, generator=g) * 2 - 1).to(dev) for s in ((3, H, W), (1, H, W), (1, H, W))]
     torch.autograd.backward([out["image"], out["alpha"], out["depth"]], cot)
@@ -54,7 +65,15 @@ def cmp(pa, pb):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "dump":
-        dump(sys.argv[2])
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("dump", "cmp"))
+    ap.add_argument("paths", nargs="+")
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--size", default="1920x1080", help="WxH")
+    ap.add_argument("--tile", type=int, default=None)
+    a = ap.parse_args()
+    if a.mode == "dump":
+        w, h = (int(v) for v in a.size.lower().split("x"))
+        dump(a.paths[0], a.n, w, h, a.tile)
     else:
-        cmp(sys.argv[2], sys.argv[3])
+        cmp(a.paths[0], a.paths[1])

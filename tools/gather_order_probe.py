@@ -41,8 +41,9 @@ with torch.no_grad():
                              op, m2, cn, cot[0], cot[1], cot[2], None, None, outputs=(img, al, dp))
 torch.cuda.synchronize()
 lib = N.load()
-fo = fr._o()[0]
+fo = fr.fo
 fws = fr.frame_ws.data_ptr()
+gst = RZ._gaussians_struct(n, model._xyz, None, model._scaling, model._rotation, model._features_dc[:, 0, :], op)
 rects = fr.rects
 ty1 = (rects[:, 1] >> 16).to(torch.int64)
 band = torch.where(vis, ty1, torch.full_like(ty1, 1 << 20))
@@ -52,15 +53,14 @@ for name, order in (("index", None), ("band", perm), ("index", None), ("band", p
     out = torch.empty((n, 10), dtype=torch.float32, device=dev)
     ga = N.GsProjectBwdArgs()
     ga.g.n = n
-    ga.vis, ga.rects, ga.pair_offset = vis.data_ptr(), fws + fo[1], fws + fo[8]
+    ga.vis, ga.rects, ga.pair_offset = vis.data_ptr(), fws + fo.rects, fws + fo.pair_offset
     ga.pair_grads = None
     ga.order = N.ptr(order)
     # the frame's partials and flags (single batch at the default tile)
     pg = torch.empty((fr.T * fr.groups, N.GS_PARTIAL_STRIDE), dtype=torch.float32, device=dev)
     ba = N.GsRenderBwdArgs()
-    fa = fr.fa
-    ba.cam, ba.fb, ba.M, ba.T, ba.tile_alt = fa.cam, fa.fb, fr.M, fr.T, fa.tile_alt
-    ba.g, ba.means2d, ba.conics, ba.vis = fa.g, fa.means2d, fa.conics, fa.vis
+    ba.cam, ba.fb, ba.M, ba.T, ba.tile_alt = fr.cam, fr.fb, fr.M, fr.T, fr.tile_alt
+    ba.g, ba.means2d, ba.conics, ba.vis = gst, m2.data_ptr(), cn.data_ptr(), vis.data_ptr()
     ba.image, ba.alpha, ba.depth = img.data_ptr(), al.data_ptr(), dp.data_ptr()
     ba.g_image, ba.g_alpha, ba.g_depth = (c.data_ptr() for c in cot)
     ba.pair_grads, ba.flags_zeroed, ba.project = pg.data_ptr(), 0, 0
