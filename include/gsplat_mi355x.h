@@ -1489,6 +1489,53 @@ typedef struct gs_mesh_args {
 gs_status gs_mesh_classify(const gs_mesh_args *a, gs_stream_t stream);
 gs_status gs_mesh_emit(const gs_mesh_args *a, gs_stream_t stream);
 
+/* ---- k-nearest neighbours (simple_knn's distCUDA2: the start-up scale of
+ * 3DGS and its descendants) -------------------------------------------------
+ * Exact k-NN of every point of a cloud among the others.  Stand-alone, stream
+ * ordered, no allocation, no atomics, no host read: a fixed launch sequence.
+ *
+ * The result is defined apart from the search.  d2(a, b) is
+ * ((dx dx) + (dy dy)) + (dz dz) of the fp32 differences, in that order,
+ * unfused -- one device function, the only place a distance is computed.  Row
+ * i of the output is the k smallest pairs (d2(p_i, p_j), j), j != i, in
+ * lexicographic order: equal distances resolve to the smaller row, and a
+ * duplicate of p_i at another row is a neighbour at distance 0.  With fewer
+ * than k other points the row is padded with +inf / -1.  mean_dist2[i] is the
+ * sum of the min(k, n - 1) distances found, ascending, in fp32, divided by
+ * their count (0 when n == 1).  So the bits do not depend on the run, the
+ * rank or the order of the input rows.
+ *
+ * The search: Morton order over the cloud's bounding box (30-bit keys, the
+ * device radix sort), boxes of 256 consecutive points with their AABBs, one
+ * workgroup per query box and one query per lane, the best K = 4, 8 or 16
+ * (the smallest >= k) in registers.  A box is passed over when its AABB's
+ * distance to the query box's AABB is strictly above the largest k-th best of
+ * the workgroup's queries, a query passes a staged box over when its own
+ * distance to the AABB is strictly above its own k-th best.  Both bounds are
+ * d2 of per-axis gaps that are no larger than the difference to any point of
+ * the box, and fp32 subtraction, squaring and adding are monotone: a bound is
+ * <= the computed d2 of every pair it stands for, with no epsilon, and on
+ * equality the box is visited.
+ *
+ * Checks, before any HIP call: a NULL struct, k outside 1..GS_KNN_MAX_K,
+ * n < 0, all three outputs NULL, and for n > 0 NULL points or a workspace
+ * that is NULL, not 16-byte aligned or smaller than gs_knn_workspace_bytes(n):
+ * GS_ERR_INVALID_ARG.  n > 2^30: GS_ERR_UNSUPPORTED (gs_knn_workspace_bytes
+ * then returns 0, as for n <= 0).  n == 0: GS_OK, nothing launched.
+ * Coordinates must be finite. */
+#define GS_KNN_MAX_K 16
+typedef struct gs_knn_args {
+  int32_t n, k;        /* 1 <= k <= GS_KNN_MAX_K */
+  const float *points; /* [n,3] */
+  float *dist2;        /* [n,k] ascending; +inf where a point has fewer than k neighbours; may be NULL */
+  int32_t *index;      /* [n,k] neighbour rows; -1 where none; may be NULL */
+  float *mean_dist2;   /* [n] mean of the min(k, n-1) distances found (0 if n == 1); may be NULL */
+  void *workspace;
+  size_t workspace_bytes;
+} gs_knn_args;
+size_t gs_knn_workspace_bytes(int32_t n);
+gs_status gs_knn(const gs_knn_args *a, gs_stream_t stream);
+
 /* ---- misc --------------------------------------------------------------- */
 int32_t gs_abi_version(void);
 const char *gs_last_error(void);

@@ -13,6 +13,7 @@ from .filter3d import Filter3D, apply_filter_3d  # noqa: F401
 from .normals import gaussian_normals, normal_consistency  # noqa: F401
 from .bilagrid import BilateralGrids, bilateral_grid_tv, slice_bilateral_grid  # noqa: F401
 from .tsdf import TSDFVolume, save_mesh_ply  # noqa: F401
+from .knn import knn, mean_knn_dist2  # noqa: F401
 from .loss import SSIMLoss, GaussianLoss, photometric_loss  # noqa: F401
 from .config import TrainingConfig, ConfigManager  # noqa: F401
 from .dataset import CameraDataset, NeRFSyntheticDataset, COLMAPDataset, load_dataset  # noqa: F401
@@ -28,4 +29,5 @@ __all__ = ["GaussianRenderer", "RenderSettings", "GaussianModel", "Camera", "Cam
            "load_dataset", "GaussianTrainer", "GraphedStep", "CameraPose", "se3_exp", "DensityStats",
            "ContributionStats", "mcmc_sample", "mcmc_relocate", "mcmc_noise", "mcmc_regularize",
            "Filter3D", "apply_filter_3d", "gaussian_normals", "normal_consistency",
-           "BilateralGrids", "bilateral_grid_tv", "slice_bilateral_grid", "TSDFVolume", "save_mesh_ply"]
+           "BilateralGrids", "bilateral_grid_tv", "slice_bilateral_grid", "TSDFVolume", "save_mesh_ply",
+           "knn", "mean_knn_dist2"]

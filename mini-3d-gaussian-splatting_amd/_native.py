@@ -422,6 +422,14 @@ class GsMeshArgs(C.Structure):
                 ("num_faces", C.c_int32), ("vertices", _vp), ("colors", _vp), ("faces", _vp)]
 
 
+GS_KNN_MAX_K = 16
+
+
+class GsKnnArgs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("k", C.c_int32), ("points", _vp), ("dist2", _vp), ("index", _vp),
+                ("mean_dist2", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
 # Every symbol the header declares (checked by tests/test_abi.py).
 EXPORTS = (
     "gs_abi_version", "gs_last_error", "gs_project_forward", "gs_radix_sort_workspace_bytes",
@@ -442,6 +450,7 @@ EXPORTS = (
     "gs_normal_consistency_forward", "gs_normal_consistency_backward",
     "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv",
     "gs_tsdf_integrate", "gs_mesh_classify", "gs_mesh_emit",
+    "gs_knn_workspace_bytes", "gs_knn",
 )
 
 _lib = None
@@ -533,6 +542,9 @@ def _declare(lib):
     lib.gs_tsdf_integrate.argtypes = [P(GsTsdfIntegrateArgs), _vp]
     lib.gs_mesh_classify.argtypes = [P(GsMeshArgs), _vp]
     lib.gs_mesh_emit.argtypes = [P(GsMeshArgs), _vp]
+    lib.gs_knn_workspace_bytes.argtypes = [C.c_int32]
+    lib.gs_knn_workspace_bytes.restype = C.c_size_t
+    lib.gs_knn.argtypes = [P(GsKnnArgs), _vp]
     for f in ("gs_project_forward", "gs_radix_sort_pairs", "gs_depth_sort_msd", "gs_bin_count", "gs_bin_emit",
               "gs_tile_ranges", "gs_blend_forward", "gs_blend_backward", "gs_blend_backward_lane_stats",
               "gs_project_backward", "gs_project_backward_pose", "gs_gather_partials", "gs_render_forward", "gs_render_backward", "gs_adam_step", "gs_project_backward_adam", "gs_loss_forward", "gs_loss_backward", "gs_densify_count", "gs_densify_emit",
@@ -544,7 +556,7 @@ def _declare(lib):
               "gs_adam_step_rows", "gs_gaussian_normals_forward", "gs_gaussian_normals_backward",
               "gs_normal_consistency_forward", "gs_normal_consistency_backward",
               "gs_bilagrid_slice_forward", "gs_bilagrid_slice_backward", "gs_bilagrid_tv",
-              "gs_tsdf_integrate", "gs_mesh_classify", "gs_mesh_emit"):
+              "gs_tsdf_integrate", "gs_mesh_classify", "gs_mesh_emit", "gs_knn"):
         getattr(lib, f).restype = C.c_int
 
 

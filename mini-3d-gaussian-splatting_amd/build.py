@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, "csrc", n) for n in (
     "gs_common.hip", "gs_project.hip", "gs_sort.hip", "gs_bin.hip", "gs_blend.hip", "gs_features.hip", "gs_adam.hip",
     "gs_loss.hip", "gs_densify.hip", "gs_mcmc.hip", "gs_filter3d.hip", "gs_normals.hip", "gs_bilagrid.hip",
-    "gs_tsdf.hip", "gs_render.hip")]
+    "gs_tsdf.hip", "gs_knn.hip", "gs_render.hip")]
 HDR = [os.path.join(ROOT, "include", "gsplat_mi355x.h"), os.path.join(HERE, "csrc", "gs_internal.h"),
        os.path.join(HERE, "csrc", "gs_device.h"), os.path.join(HERE, "csrc", "gs_blend_device.h"),
        os.path.join(HERE, "csrc", "gs_gather_device.h")]

@@ -128,6 +128,10 @@ class TrainingConfig:
     bilateral_grid_lr: float = 2e-3
     bilateral_grid_warmup: int = 1000
     lambda_tv: float = 10.0
+    # the start-up scales (GaussianModel.create_from_points / create_from_random): "extent", one scale for
+    # every Gaussian (1 % / 2 % of the cloud's extent), or "knn", 3DGS's rule -- each Gaussian the size of its
+    # neighbourhood, the root of the mean squared distance to its three nearest points (knn.mean_knn_dist2)
+    scale_init: str = "extent"
 
     def __post_init__(self):
         # (a YAML file holds the iterations as a list)
@@ -191,6 +195,8 @@ class TrainingConfig:
         lam = float(self.lambda_tv)
         if not (lam >= 0.0 and lam != float("inf")):
             raise ValueError(f"lambda_tv must be finite and >= 0, got {self.lambda_tv!r}")
+        if self.scale_init not in SCALE_INITS:
+            raise ValueError(f"scale_init must be one of {SCALE_INITS}, got {self.scale_init!r}")
         nf = self.distortion_near_far
         if nf is not None:
             ok = isinstance(nf, (tuple, list)) and len(nf) == 2 and all(isinstance(v, (int, float)) for v in nf)
@@ -213,6 +219,7 @@ class TrainingConfig:
 
 
 DENSIFY_CRITERIA = ("xyz_grad", "screen", "mcmc")
+SCALE_INITS = ("extent", "knn")  # scale_init, here and in GaussianModel.create_from_*
 
 
 def _need_yaml():

@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
+from .config import SCALE_INITS
 from .rasterizer import ContributionStats, DensityStats
 
 
@@ -110,10 +111,30 @@ class GaussianModel(nn.Module):
         self.density_stats = DensityStats(n, dev, self.density_abs_grad)
         self._contribution_stats = None
 
+    @staticmethod
+    def _check_scale_init(scale_init) -> None:
+        if scale_init not in SCALE_INITS:
+            raise ValueError(f"scale_init must be one of {SCALE_INITS}, got {scale_init!r}")
+
+    @staticmethod
+    def _knn_scaling(points: torch.Tensor) -> torch.Tensor:
+        """3DGS's start-up scale: log of the root of the mean squared distance
+        to the three nearest points (simple_knn's distCUDA2), the same on all
+        three axes.  knn.mean_knn_dist2 defines its result without reference to
+        the search, so every rank of a data-parallel run that initialises from
+        the same points gets the same bits: no broadcast is needed."""
+        from .knn import mean_knn_dist2
+        d2 = torch.clamp_min(mean_knn_dist2(points, 3), 1e-7)
+        return torch.log(torch.sqrt(d2))[:, None].repeat(1, 3)
+
     @torch.no_grad()
     def create_from_random(self, num_points: int, scene_extent: float = 1.0,
-                           device=None, generator: Optional[torch.Generator] = None) -> None:
-        """gaussian_model.py:78-98"""
+                           device=None, generator: Optional[torch.Generator] = None,
+                           scale_init: str = "extent") -> None:
+        """gaussian_model.py:78-98.  scale_init "knn": the scales of
+        create_from_points(scale_init="knn") instead of 2 % of the extent (the
+        draws, and so everything else, stay what they are)."""
+        self._check_scale_init(scale_init)
         dev = device if device is not None else self._xyz.device
         kw = dict(generator=generator)
         xyz = (torch.rand(num_points, 3, **kw) - 0.5) * (2.0 * scene_extent)
@@ -122,12 +143,19 @@ class GaussianModel(nn.Module):
         scaling = torch.full((num_points, 3), math.log(0.02 * scene_extent))
         rot = F.normalize(torch.randn(num_points, 4, **kw), dim=-1)
         opacity = torch.full((num_points, 1), -2.0)
+        if scale_init == "knn":  # (searched where the model lives: the CPU path is O(N^2))
+            scaling = self._knn_scaling(xyz.to(dev))
         self._set(*(t.to(dev) for t in (xyz, fdc, frest, scaling, rot, opacity)))
 
     @torch.no_grad()
     def create_from_points(self, points: torch.Tensor, colors: Optional[torch.Tensor] = None,
-                           spatial_lr_scale: float = 1.0) -> None:
-        """create_from_pcd (gaussian_model.py:42-76) from in-memory points."""
+                           spatial_lr_scale: float = 1.0, scale_init: str = "extent") -> None:
+        """create_from_pcd (gaussian_model.py:42-76) from in-memory points.
+        scale_init: "extent", every Gaussian 1 % of the cloud's extent, or
+        "knn", 3DGS's rule: each Gaussian the size of its neighbourhood,
+        sqrt(max(mean squared distance to its 3 nearest points, 1e-7)).  Only
+        _scaling differs between the two: the rotations are the same draws."""
+        self._check_scale_init(scale_init)
         points = torch.as_tensor(points, dtype=torch.float32)
         n, dev = points.shape[0], points.device
         if n == 0:
@@ -135,23 +163,27 @@ class GaussianModel(nn.Module):
         colors = torch.ones(n, 3, device=dev) if colors is None else torch.as_tensor(colors, dtype=torch.float32)
         extent = (points.max(0).values - points.min(0).values).mean().item()
         base = 0.01 * max(extent, 1e-2) * spatial_lr_scale
-        self._set(points, colors[:, None, :], torch.zeros(n, 15, 3, device=dev),
-                  torch.full((n, 3), math.log(base), device=dev),
+        scaling = torch.full((n, 3), math.log(base), device=dev) if scale_init == "extent" else \
+            self._knn_scaling(points)
+        self._set(points, colors[:, None, :], torch.zeros(n, 15, 3, device=dev), scaling,
                   F.normalize(torch.randn(n, 4, device=dev), dim=-1), torch.full((n, 1), 0.5, device=dev))
 
     @torch.no_grad()
-    def create_from_pcd(self, pcd_path: str, spatial_lr_scale: float = 1.0, device=None) -> None:
+    def create_from_pcd(self, pcd_path: str, spatial_lr_scale: float = 1.0, device=None,
+                        scale_init: str = "extent") -> None:
         """gaussian_model.py:42-76: initialise from a point-cloud file (the
         formats of dataset.load_point_cloud; the reference's own loader call,
         IOUtils.load_pcd, does not exist)."""
         from .dataset import load_point_cloud
+        self._check_scale_init(scale_init)
         pts, cols = load_point_cloud(pcd_path)
         if pts.shape[0] == 0:
             raise ValueError("No points found in the PCD file.")
         dev = torch.device(device) if device is not None else (
             torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
         self.create_from_points(torch.from_numpy(pts).to(dev),
-                                None if cols is None else torch.from_numpy(cols).to(dev), spatial_lr_scale)
+                                None if cols is None else torch.from_numpy(cols).to(dev), spatial_lr_scale,
+                                scale_init)
 
     # -- accessors (gaussian_model.py:101-128) ------------------------------
     @property

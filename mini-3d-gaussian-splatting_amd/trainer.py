@@ -118,10 +118,12 @@ class GaussianTrainer:
         gen = torch.Generator().manual_seed(c.seed)
         if self.dataset.points is not None and len(self.dataset.points):
             g.create_from_points(torch.from_numpy(self.dataset.points).to(dev),
-                                 torch.from_numpy(self.dataset.colors).to(dev) if self.dataset.colors is not None else None)
+                                 torch.from_numpy(self.dataset.colors).to(dev) if self.dataset.colors is not None else None,
+                                 scale_init=c.scale_init)
         else:
             # Blender scenes have no points: uniform in [-1.3, 1.3]^3 (the NeRF-synthetic object box)
-            g.create_from_random(c.num_random_points, scene_extent=1.3, device=dev, generator=gen)
+            g.create_from_random(c.num_random_points, scene_extent=1.3, device=dev, generator=gen,
+                                 scale_init=c.scale_init)
         self.gaussians = g
         self.optimizer = GaussianOptimizer(g, c)
         self.optimizer.setup_optimizer()
